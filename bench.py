@@ -1,15 +1,19 @@
 """Headline benchmark (BASELINE.json): stereo pairs/s and ms per GRU iteration of coreContinuous_IGEV inference on a
 960x540 SceneFlow-shape synthetic pair, 32 iterations (cfg 2), fp32 storage.
 
-    python bench.py [--gpus N --steps K --warmup W]            N > 1: this process spawns N ranks itself (one per GPU)
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+                                                               N > 1: this process spawns N ranks itself (one per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...     (the driver's form)
 
 One process per GPU over RCCL; every rank runs the same per-GPU workload on its own pair (independent units, no
 data-path collective: "replicas", weak scaling).  A step = one full forward pass (backbones on PyTorch-ROCm/MIOpen, hot path
-on libanystereo_hip.so) with inputs resident in HBM.  `value` is the median of three timed blocks of --steps steps (`value_spread`).
+on libanystereo_hip.so) with inputs resident in HBM.  A plain run sets up, runs W warm-up steps, times exactly K steps and prints
+the headline (`value`, `ms_per_step`); `--dump-outputs DIR` then also writes the disparities of the last timed step as
+DIR/disparity.npy (`--mode train`: loss, metrics and the updated parameters), the same inputs and weights on every run.
+Everything below is measured only with `--full`, where `value` is the median of three timed blocks of K steps (`value_spread`).
 With a process group (N > 1, or any N under torch.distributed.run) the same ranks then run the cfg-4 TRAINING leg (`train_leg`:
 graphed steps, one flat RCCL all-reduce per step) and `train_mode` carries its N-rank figures; one rank without a launcher runs that
-leg as a child process.  Rank 0 prints ONE JSON line (stdout carries nothing else).  Extra objects on that line:
+leg as a child process.  Rank 0 prints ONE JSON line (stdout carries nothing else).  Extra objects on the --full line:
   pass_phases     pre-loop / loop / upsampler wall time of a replayed pass from marker kernels inside the graph (no profiler)
   roofline        dominant kernel (by time), HIP events on its launch stream
   rooflines       the same figure for every hot kernel class; HBM-bound ones warm (working set in the Infinity Cache),
@@ -121,7 +125,37 @@ def parse(argv=None):
                     help="train mode: the timed steps and the dominant kernel's roofline only (no eager comparison, no CPU baseline): "
                          "what the default inference run starts as a child process for its `train_mode` object")
     ap.add_argument("--no-train-mode", action="store_true", help="infer mode: skip the `train_mode` object (cfg 4, 1 rank, child process)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also every side measurement (CPU baseline, other precisions and configurations, rooflines, per-kernel times, "
+                         "the training leg, median of %d timed blocks); without it the run times --steps steps of the headline only"
+                         % TIMED_BLOCKS)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    a = ap.parse_args(argv)
+    if not a.full:  # a plain run measures its headline and nothing else; under --full the --no-* flags drop single side legs
+        a.no_batched = a.no_cpu_baseline = a.no_extras = a.no_train_mode = True
+    return a
+
+
+DUMP_LIMIT_BYTES = 60_000_000  # what --dump-outputs may write in all (headers included, under 64 MB)
+
+
+def dump_outputs(path: str, arrays: dict):
+    """--dump-outputs: one DIR/<name>.npy per array, float32 (float64 stays float64).  Above DUMP_LIMIT_BYTES in all, every array
+    is thinned to the same fraction by a fixed, seeded choice of its (flattened) elements, so that two builds run with the same
+    arguments write files that compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrs = {}
+    for name, v in arrays.items():
+        v = np.asarray(v.detach().cpu() if hasattr(v, "detach") else v)
+        arrs[name] = v.astype(np.float64 if v.dtype == np.float64 else np.float32)
+    total = sum(v.nbytes for v in arrs.values())
+    for name, v in arrs.items():
+        if total > DUMP_LIMIT_BYTES:
+            keep = max(1, v.size * (DUMP_LIMIT_BYTES - 4096) // total)
+            v = v.reshape(-1)[np.sort(np.random.default_rng(0).choice(v.size, keep, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), v)
 
 
 # ------------------------------------------------------------------------------------------------------------------
@@ -301,6 +335,7 @@ def dry_train_main(a, rank, world):
         sums = [v.tolist() for v in gs]
         cpu_sets = [None] * world
         td.all_gather_object(cpu_sets, RANK_CPUS)
+    if td and a.full:
         dt_ns, _ = timed(max(2, a.steps), sync_grads=False)  # last: the ranks' parameters diverge from here on
         t2 = torch.tensor([dt_ns], dtype=torch.float64)
         td.all_reduce(t2, op=td.ReduceOp.MAX)
@@ -479,7 +514,7 @@ def train_mode_child(a, steps=5, warmup=4, timeout=420):
     `steps` graphed steps.  Returns the child's line reduced to what the driver should see, or {"error": ...}."""
     import subprocess
     cmd = [sys.executable, os.path.abspath(__file__), "--mode", "train", "--gpus", "1", "--steps", str(steps), "--warmup", str(warmup),
-           "--train-quick", "--no-cpu-baseline"]
+           "--train-quick", "--no-cpu-baseline", "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "LOCAL_WORLD_SIZE", "MASTER_PORT")}
     t0 = time.perf_counter()
     try:
@@ -808,15 +843,18 @@ def train_main(a, rank, world, local):
         t0 = time.perf_counter()
         for _ in range(n):
             torch.cuda._sleep(2000)  # ~1 us `spin_kernel`: step marker for tools/profile_train.sh
-            loss, _ = tr.step(batch, sync_grads=sync_grads)
+            last = tr.step(batch, sync_grads=sync_grads)
         torch.cuda.synchronize()
         if dist:
             td.barrier()
         torch.cuda.synchronize()
-        return time.perf_counter() - t0, loss
+        return time.perf_counter() - t0, last
 
-    dt, loss = timed(a.steps)
+    dt, (loss, metrics) = timed(a.steps)
     losses.append(float(loss))
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"loss": loss, **(metrics or {}),
+                                      "parameters": torch.cat([p.detach().reshape(-1) for p in model.parameters()])})
     per_rank = [dt]
     overlap = None
     if dist:
@@ -826,6 +864,7 @@ def train_main(a, rank, world, local):
         per_rank = [float(g.item()) for g in gathered]
         td.all_reduce(t, op=td.ReduceOp.MAX)
         dt = float(t.item())
+    if dist and a.full:
         # what the gradient all-reduce costs on the critical path: the same steps with DDP's reducer off (no_sync: every
         # rank steps on its local gradient) — outside the timed region, reported only
         n2 = max(2, min(a.steps, 5))
@@ -1218,18 +1257,20 @@ def infer_main(a, rank, world, local):
         td.barrier()
     torch.cuda.synchronize()
     from anystereo.harness import timing
-    if not run.graph:
+    if not run.graph and a.full:
         timing.enable(True)       # HIP events around every hot-kernel launch, on the launch stream
-    # `value` = the MEDIAN of `TIMED_BLOCKS` timed blocks; each block times exactly `--steps` steps between barrier +
-    # synchronize on both sides and is reduced with MAX over the ranks.  Box-to-box and run-to-run spread of this workload is a
-    # few per cent (profiles/r05_bench_lease_spread.txt): one block is one sample of it, the line carries all of them.
+    # Each timed block times exactly `--steps` steps between barrier + synchronize on both sides and is reduced with MAX over the
+    # ranks.  A plain run times one block; with --full `value` is the MEDIAN of `TIMED_BLOCKS` blocks.  Box-to-box and run-to-run
+    # spread of this workload is a few per cent (profiles/r05_bench_lease_spread.txt): one block is one sample of it, the full line
+    # carries all of them.
+    blocks = TIMED_BLOCKS if a.full else 1
     block_dt, block_tel, block_own = [], [], []
-    for _ in range(TIMED_BLOCKS):
+    for _ in range(blocks):
         torch.cuda.synchronize()
         if dist:
             td.barrier()
         torch.cuda.synchronize()
-        telemetry = GpuTelemetry(local).start()
+        telemetry = GpuTelemetry(local).start() if a.full else None
         t0 = time.perf_counter()
         for _ in range(a.steps):
             out = run.step()
@@ -1239,15 +1280,15 @@ def infer_main(a, rank, world, local):
             td.barrier()
         torch.cuda.synchronize()
         d_blk = time.perf_counter() - t0
-        block_tel.append(telemetry.stop())
+        block_tel.append(telemetry.stop() if telemetry else {})
         if dist:
             t = torch.tensor([d_blk], device=dev, dtype=torch.float64)
             td.all_reduce(t, op=td.ReduceOp.MAX)
             d_blk = float(t.item())
         block_dt.append(d_blk)
         block_own.append(d_own)
-    order = sorted(range(TIMED_BLOCKS), key=lambda i: block_dt[i])
-    mid = order[TIMED_BLOCKS // 2]      # the same index on every rank: block_dt is the all-reduced figure
+    order = sorted(range(blocks), key=lambda i: block_dt[i])
+    mid = order[blocks // 2]      # the same index on every rank: block_dt is the all-reduced figure
     dt, telemetry = block_dt[mid], block_tel[mid]
     out_split = out.float().cpu() if precision == "split" else None
     out_this = out.float().cpu()
@@ -1258,6 +1299,25 @@ def infer_main(a, rank, world, local):
         td.all_gather(gathered, t)
         per_rank = [float(g.item()) for g in gathered]
     assert torch.isfinite(out).all()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"disparity": out_this})
+    headline = {
+        "metric": "stereo pairs/sec (coreContinuous_IGEV inference, 32-iter GRU, 960x540)",
+        "value": round(world * nb * a.steps / dt, 4), "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32" if precision == "fp32" else "f32 (3xf16 split-precision MFMA, fp32 accumulate)", "data": "synthetic",
+        "config": {"workload": f"{wl.what} (padded {run.wp}x{run.hp}), {wl.iters} GRU iters, scale {wl.scale}, Q={run.Q} queries, "
+                               f"{nb} pair(s) per GPU, random-init weights", "name": wl.name, "pairs_per_gpu": nb,
+                   "parallelism": f"replicas x{world}", "gru_loop": "hipGraph" if run.graph else "eager"},
+        "per_rank_pairs_per_s": [round(nb * a.steps / v, 4) for v in per_rank],
+    }
+    if not a.full:
+        if rank == 0:
+            emit(dict(headline, library=_lib.library_info()))
+        if dist:
+            td.barrier()
+            td.destroy_process_group()
+        return
     if run.graph:
         kstats, ksteps = kernel_stats(run, passes=2)
     else:
@@ -1303,17 +1363,8 @@ def infer_main(a, rank, world, local):
     if dist and not a.no_train_mode and wl.name == "cfg2":
         leg_guard = _LegWatchdog(rank, float(os.environ.get("ANYSTEREO_TRAIN_LEG_TIMEOUT", "240")))
         if rank == 0:  # the contract's fields of the headline, known before the leg starts: what the watchdog prints if it must
-            leg_guard.rearm({
-                "metric": "stereo pairs/sec (coreContinuous_IGEV inference, 32-iter GRU, 960x540)",
-                "value": round(world * nb * a.steps / dt, 4), "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-                "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-                "dtype": "f32" if precision == "fp32" else "f32 (3xf16 split-precision MFMA, fp32 accumulate)", "data": "synthetic",
-                "config": {"workload": f"{wl.what} (padded {run.wp}x{run.hp}), {wl.iters} GRU iters, scale {wl.scale}, Q={run.Q} queries, "
-                                       f"{nb} pair(s) per GPU, random-init weights", "name": wl.name, "pairs_per_gpu": nb,
-                           "parallelism": f"replicas x{world}", "gru_loop": "hipGraph" if run.graph else "eager"},
-                "per_rank_pairs_per_s": [round(nb * a.steps / v, 4) for v in per_rank],
-                "ms_per_gru_iter": None if ms_iter is None else round(ms_iter, 4),
-                "roofline": None, "cpu_baseline": None, "truncated": "printed by the training leg's watchdog"})
+            leg_guard.rearm(dict(headline, ms_per_gru_iter=None if ms_iter is None else round(ms_iter, 4),
+                                 roofline=None, cpu_baseline=None, truncated="printed by the training leg's watchdog"))
         try:
             train_mode_n = train_leg(a, rank, world, local, td, dev)
         except Exception as ex:  # a rank-local failure outside the agreed phases
@@ -1488,10 +1539,7 @@ def infer_main(a, rank, world, local):
                 train_mode = train_mode_child(a)
             except Exception as ex:
                 train_mode = {"error": repr(ex)[:300]}
-        line = {
-            "metric": "stereo pairs/sec (coreContinuous_IGEV inference, 32-iter GRU, 960x540)",
-            "value": round(world * nb * a.steps / dt, 4), "unit": "pairs/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
-            "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        line = dict(headline, **{
             "timed_blocks": TIMED_BLOCKS,
             "value_spread": {"how": f"`value` / `ms_per_step` = the median of {TIMED_BLOCKS} timed blocks of {a.steps} steps each (barrier + synchronize "
                                     "on both sides of every block, MAX over ranks per block)",
@@ -1499,11 +1547,6 @@ def infer_main(a, rank, world, local):
                              "min": round(world * nb * a.steps / max(block_dt), 4), "max": round(world * nb * a.steps / min(block_dt), 4),
                              "median": round(world * nb * a.steps / dt, 4),
                              "telemetry_per_block": block_tel},
-            "dtype": "f32" if precision == "fp32" else "f32 (3xf16 split-precision MFMA, fp32 accumulate)", "data": "synthetic",
-            "config": {"workload": f"{wl.what} (padded {run.wp}x{run.hp}), {wl.iters} GRU iters, scale {wl.scale}, Q={run.Q} queries, "
-                                   f"{nb} pair(s) per GPU, random-init weights", "name": wl.name, "pairs_per_gpu": nb,
-                       "parallelism": f"replicas x{world}", "gru_loop": "hipGraph" if run.graph else "eager"},
-            "per_rank_pairs_per_s": [round(nb * a.steps / v, 4) for v in per_rank],
             "host": {"cpus_per_rank": len(RANK_CPUS or []), "pinned": world > 1 and os.environ.get("ANYSTEREO_PIN", "1") != "0",
                      "torch_threads": torch.get_num_threads(), **telemetry},
             "library": _lib.library_info(),
@@ -1525,7 +1568,7 @@ def infer_main(a, rank, world, local):
             "throughput_mode": batched,
             "train_mode": train_mode,
             "cpu_baseline": cpu,
-        }
+        })
         emit(line)
     if dist:
         td.barrier()

@@ -241,7 +241,7 @@ def test_bench_launcher_spawns_ranks_world2():
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""   # also on a GPU box: protocol rehearsal only
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"],
                        capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -274,8 +274,8 @@ def test_bench_train_launcher_dry_protocol_world2():
     root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "train", "--gpus", "2", "--steps", "2", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=300, env=env)
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "train", "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, timeout=300, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -302,8 +302,8 @@ def test_bench_under_torch_distributed_run_world2():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1"],
-                       capture_output=True, text=True, timeout=300, env=env, cwd=root)
+                        "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
+                        "--full"], capture_output=True, text=True, timeout=300, env=env, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout
@@ -331,3 +331,45 @@ def test_bench_train_leg_watchdog_prints_stashed_line():
     code2 = code.replace("_LegWatchdog(0, 0.3)", "_LegWatchdog(1, 0.3)")
     r2 = subprocess.run([sys.executable, "-c", code2], capture_output=True, text=True, timeout=60)
     assert r2.returncode == 0 and r2.stdout.strip() == ""  # other ranks leave silently
+
+
+def test_bench_plain_run_skips_side_legs_world2():
+    """A plain `python bench.py --gpus 2` (no --full) without a GPU: the launch protocol and its timed steps, and no training leg."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
+    env["CUDA_VISIBLE_DEVICES"] = env["HIP_VISIBLE_DEVICES"] = ""
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=300, env=env)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+    assert len(lines) == 1, r.stdout
+    d = json.loads(lines[0])
+    assert d["n_gpus"] == 2 and d["steps"] == 3 and d["ms_per_step"] > 0 and d["train_mode"] is None
+
+
+def test_bench_dump_outputs_cap_and_seeded_sample(tmp_path):
+    """bench.dump_outputs: float32 files (float64 kept), at most 64 MB in all; a larger output is thinned by the same seeded choice
+    of elements on every call, so two runs compare element for element."""
+    import sys
+
+    import numpy as np
+    root = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+    sys.path.insert(0, root)
+    import bench
+    small = {"loss": torch.tensor(1.25, dtype=torch.float64), "disparity": torch.arange(12, dtype=torch.float16).reshape(1, 1, 12)}
+    bench.dump_outputs(str(tmp_path / "s"), small)
+    assert np.load(tmp_path / "s" / "loss.npy").dtype == np.float64
+    disp = np.load(tmp_path / "s" / "disparity.npy")
+    assert disp.dtype == np.float32 and disp.shape == (1, 1, 12) and (disp.ravel() == np.arange(12)).all()
+    big = {"a": torch.arange(12_000_000, dtype=torch.float32), "b": torch.arange(6_000_000, dtype=torch.float64)}
+    for sub in ("x", "y"):
+        bench.dump_outputs(str(tmp_path / sub), big)
+    files = {n: tmp_path / "x" / (n + ".npy") for n in big}
+    assert sum(f.stat().st_size for f in files.values()) <= 64 * 10 ** 6
+    for n, f in files.items():
+        v = np.load(f)
+        assert v.dtype == (np.float64 if n == "b" else np.float32) and 0 < v.size < big[n].numel()
+        assert (np.diff(v) > 0).all() and (v == np.load(tmp_path / "y" / (n + ".npy"))).all()

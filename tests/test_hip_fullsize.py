@@ -670,7 +670,7 @@ def test_gru_convs_cfg3_cfg5_sizes(hw):
 
 @pytest.mark.gpu
 def test_default_bench_command_produces_its_line():
-    """`python bench.py` with its default legs (split-precision headline, fp32 mode, reduced precision, cfg 1/3/5, batched) runs to
+    """`python bench.py --full` with its side legs (split-precision headline, fp32 mode, reduced precision, cfg 1/3/5, batched) runs to
     the end in a fresh process and prints ONE parseable JSON line — every leg captures and replays its own hipGraph, which is
     where a fork without a join shows up.  (One timed step per leg; the CPU baseline is skipped.)"""
     import json
@@ -678,7 +678,7 @@ def test_default_bench_command_produces_its_line():
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--full"],
                        capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
@@ -697,7 +697,7 @@ def test_default_bench_command_produces_its_line():
 
 @pytest.mark.gpu
 def test_train_bench_command_produces_its_line():
-    """`python bench.py --mode train` (one rank, no launcher) in a fresh process: one parseable line with a finite loss."""
+    """`python bench.py --mode train --full` (one rank, no launcher) in a fresh process: one parseable line with a finite loss."""
     import json
     import math
     import os
@@ -705,7 +705,7 @@ def test_train_bench_command_produces_its_line():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "train", "--steps", "1", "--warmup", "1",
-                        "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=root)
+                        "--no-cpu-baseline", "--full"], capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -732,7 +732,7 @@ def test_bench_command_under_the_drivers_launcher_one_rank():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT", "MASTER_ADDR")}
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1",
                         "--master-port", str(port), os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
-                        "--no-cpu-baseline", "--no-extras", "--no-batched"], capture_output=True, text=True, timeout=600, cwd=root, env=env)
+                        "--no-cpu-baseline", "--no-extras", "--no-batched", "--full"], capture_output=True, text=True, timeout=600, cwd=root, env=env)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -753,3 +753,29 @@ def test_bench_command_under_the_drivers_launcher_one_rank():
     assert tm["exchange_ms"] > 0 and tm["grad_bytes"] > 4e7 and tm["loss_finite"] is True
     assert len(tm["ranks_seen"]) == 1 and tm["ranks_seen"][0]["device_index"] == 0 and tm["distinct_devices"] == 1
     assert len(tm["one_rank_ms_per_step"]) == 1 and 0.5 < tm["scaling"] < 1.5
+
+
+@pytest.mark.gpu
+def test_plain_bench_command_times_its_steps_and_dumps_outputs(tmp_path):
+    """`python bench.py --steps K --warmup W --dump-outputs DIR` (no --full): one line with the headline fields, K timed steps and
+    none of the side legs; DIR/disparity.npy holds the last timed step's disparities, float32, one per query."""
+    import json
+    import math
+    import os
+    import subprocess
+    import sys
+
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                        "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert r.returncode == 0, r.stderr[-2000:]
+    lines = [ln for ln in r.stdout.strip().splitlines() if ln.startswith("{")]
+    assert len(lines) == 1
+    d = json.loads(lines[0])
+    assert d["unit"] == "pairs/s" and d["value"] > 0 and d["higher_is_better"] is True and d["steps"] == 3
+    assert math.isclose(d["ms_per_step"], 1e3 / d["value"], rel_tol=1e-3) and "f32" in d["dtype"]
+    assert d["library"]["matches_sources"] is True
+    assert not {"fp32_mode", "other_configs", "train_mode", "cpu_baseline", "rooflines", "value_spread"} & set(d)
+    disp = np.load(tmp_path / "disparity.npy")
+    assert disp.dtype == np.float32 and disp.shape == (1, 1, 518400) and np.isfinite(disp).all()

@@ -9,7 +9,7 @@ for i in 1 2 3; do
       lookup) export AS_LOOKUP_DIRECT=1 AS_CONV_WIDE64=0;;
       both) export AS_LOOKUP_DIRECT=1 AS_CONV_WIDE64=1;;
     esac
-    python $ROOT/bench.py --no-cpu-baseline --no-extras --no-batched --steps 10 --warmup 3 2>/dev/null | python -c "
+    python $ROOT/bench.py --full --no-cpu-baseline --no-extras --no-batched --steps 10 --warmup 3 2>/dev/null | python -c "
 import json, sys
 d = json.loads(sys.stdin.read().strip().splitlines()[-1])
 k = d['kernel_times_us']

@@ -8,7 +8,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 OUT=$ROOT/gpurun_out
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $OUT/_kt -- python $ROOT/bench.py --mode train --steps 3 --warmup 2 --no-extras --no-cpu-baseline > $OUT/${TAG}_train_bench_under_rocprof.json 2>/dev/null
+rocprofv3 --kernel-trace --output-format csv -d $OUT/_kt -- python $ROOT/bench.py --full --mode train --steps 3 --warmup 2 --no-extras --no-cpu-baseline > $OUT/${TAG}_train_bench_under_rocprof.json 2>/dev/null
 python - <<PY
 import csv, glob, collections
 f = glob.glob("$OUT/_kt/*/*kernel_trace.csv")[0]

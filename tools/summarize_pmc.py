@@ -115,7 +115,7 @@ def main():
             res[cls]["wide"] = wide
     need = compulsory_inputs(h, w)
     summary = {"_meta": {"src_hash": src_hash(), "collected": datetime.datetime.utcnow().strftime("%Y-%m-%dT%H:%MZ"),
-                         "command": "bench.py --no-cpu-baseline --no-batched --no-extras --no-graph --steps 1 --warmup 1 under "
+                         "command": "bench.py --full --no-cpu-baseline --no-batched --no-extras --no-graph --steps 1 --warmup 1 under "
                                     "rocprofv3 --pmc FETCH_SIZE and (separately) --pmc WRITE_SIZE",
                          "correction": "FETCH_SIZE x2 for classes with 16 B/lane reads (MI355X_MICROARCH.md §HBM); "
                                        "KiB -> bytes x1024", "quarter_res_map": [h, w]}}
