@@ -142,6 +142,9 @@ SIGNATURES = {
     "as_interp_bilinear_ac_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "as_gwc_volume_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "as_disparity_regression_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "as_init_head_partial_elems": (C.c_int64, [_i, _i, _i]),
+    "as_init_head_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "as_init_head_wgrad_reduce": (_i, [_vp, _i, _vp, _vp]),
     "as_liif_gather_bwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "as_liif_gather_bwd_det": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "as_gru_gates_zr": (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -154,6 +154,34 @@ class DisparityRegression(torch.autograd.Function):
         return d_cost, None
 
 
+# ---- a5': classifier Conv3d + softmax + disparity regression, the IGEV init-disparity head (continuous_IGEVstereo.py:267-268) ---
+class InitDispHead(torch.autograd.Function):
+    """init_disp [B,1,H,W] = disparity_regression(softmax_D(classifier(geo))) for geo [B,8,D,H,W], weight [1,8,3,3,3].
+    Forward: exactly the kernels of the composition it replaces (nn/blocks.py::_SearchedConv's convolution, then
+    ops.disparity_regression with the softmax) — the same bits.  Backward: csrc/init_head.hip, d_geo and the weight gradient from
+    one pass over geo (instead of MIOpen's convolution backward behind DisparityRegression's backward).  Under autocast the saved
+    operands are fp16: the kernel gets them in fp32, the gradients go back in the input dtypes."""
+
+    @staticmethod
+    def forward(ctx, geo, weight):
+        from .nn import blocks as B
+        from .harness.timing import scope
+        ctx.in_dtypes = (geo.dtype, weight.dtype)
+        cost, x, w = B.searched_conv_forward(geo, weight, None, ([1, 1, 1], [1, 1, 1], [1, 1, 1], False, [0, 0, 0], 1))
+        cost = cost.squeeze(1).float().contiguous()
+        with scope("disparity_regression"):
+            out = ops.disparity_regression(cost, apply_softmax=True)
+        ctx.save_for_backward(x, w, cost)
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        x, w, cost = ctx.saved_tensors
+        d_geo, d_w = ops.init_head_bwd(_c(x), _c(w), cost, _c(d_out))
+        dx, dw = ctx.in_dtypes
+        return (d_geo.to(dx) if ctx.needs_input_grad[0] else None, d_w.to(dw) if ctx.needs_input_grad[1] else None)
+
+
 # ---- a12/a13: cat(x, affinity(x.detach())) (liif.py:496-499) ----------------------------------------------------
 class StructureFeature(torch.autograd.Function):
     @staticmethod

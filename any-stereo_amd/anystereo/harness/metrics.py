@@ -1,6 +1,7 @@
 """§8(f2)/(f3): the training loss and the evaluation metrics that define "parity" for Any-Stereo.
 
 sequence_loss_multiscale  train_continuous_IGEV.py:68-94   (exponentially weighted masked L1 over the GRU predictions)
+sequence_loss_multiscale_superinit  train_continuous_IGEV.py:96-122  (+ smooth-L1 on init_disp at 1/4 resolution: --supervise_init)
 fetch_optimizer           train_continuous_IGEV.py:125-134 (AdamW + linear OneCycleLR)
 EPE / D1 / Thres          metrics_utils/metrics.py:66-90 with the per-image wrapper :22-42
 Host-side tensor code (any device); pinned by tests/golden/loss_metrics.npz captured from the reference.
@@ -58,6 +59,32 @@ def sequence_loss_multiscale(disp_preds, disp_gt, valid, loss_gamma=0.9, max_dis
     return loss, metrics
 
 
+def sequence_loss_multiscale_superinit(init_disp_preds, low_dispgt, disp_preds, disp_gt, valid, loss_gamma=0.9, max_disp=700,
+                                       sync_free=False):
+    """sequence_loss_multiscale plus 1.0 * smooth_l1(init_disp[valid_low], low_dispgt[valid_low]) (beta 1, mean) with
+    valid_low = low_dispgt < max_disp / 4 — no `> 0` test, as in the reference (train_continuous_IGEV.py:96-122; chosen at :220-221
+    under --supervise_init).  init_disp_preds, low_dispgt: [B,h,w] (the model's init_disp, squeezed; stereo_datasets.py:151-156).
+    Returns (loss, metrics) with the metrics of the GRU predictions.  With no valid low-resolution pixel the loss is NaN (the
+    mean over an empty set), in both forms.
+    sync_free=False: the reference's statement (boolean indexing, `.item()` metrics).  sync_free=True: masked sums over a count, no
+    host synchronisation (capturable); the mask is a SELECT on sanitised ground truth, never a product (Middlebury ground truth holds
+    inf: inf * 0 = NaN)."""
+    import torch.nn.functional as F
+    valid_low = low_dispgt < (max_disp / 4.0)
+    assert init_disp_preds.shape == low_dispgt.shape, [init_disp_preds.shape, low_dispgt.shape]
+    if sync_free:
+        zero = torch.zeros((), dtype=init_disp_preds.dtype, device=init_disp_preds.device)
+        low = torch.where(valid_low, low_dispgt.to(init_disp_preds.dtype), zero)
+        diff = torch.where(valid_low, init_disp_preds - low, zero)
+        ad = diff.abs()
+        sl1 = torch.where(ad < 1.0, 0.5 * diff * diff, ad - 0.5)  # smooth_l1, beta = 1
+        init_loss = torch.where(valid_low, sl1, zero).sum() / valid_low.sum().to(init_disp_preds.dtype)
+    else:
+        init_loss = F.smooth_l1_loss(init_disp_preds[valid_low.bool()], low_dispgt[valid_low.bool()], reduction="mean")
+    loss, metrics = sequence_loss_multiscale(disp_preds, disp_gt, valid, loss_gamma=loss_gamma, max_disp=max_disp, sync_free=sync_free)
+    return 1.0 * init_loss + loss, metrics
+
+
 def fetch_optimizer(lr, wdecay, num_steps, params, lr_fixed=False, capturable=False):
     """AdamW + linear OneCycleLR (train_continuous_IGEV.py:125-134).  capturable=True: the optimizer's step counter and its
     learning rate live on the device (the scheduler writes the tensor), so `optimizer.step()` can be captured into a hipGraph."""
@@ -104,7 +131,7 @@ def thres_metric(d_est, d_gt, mask, thres):
 
 
 def train_step(model, optimizer, scheduler, scaler, batch, train_iters, max_disp=192, clip=1.0, loss_scale=1.0, sync_free_loss=False,
-               should_step=None, phase="all"):
+               should_step=None, phase="all", supervise_init=False):
     """One optimisation step with the reference's ordering (train_continuous_IGEV.py:214-239, multi_training branch):
     zero_grad -> forward(train mode) -> sequence_loss_multiscale with valid = (gt < 512) & (gt > 0) -> scaled backward ->
     unscale -> clip_grad_norm_(1.0) -> optimizer step -> scheduler step (unless fixed lr) -> scaler update.
@@ -116,16 +143,30 @@ def train_step(model, optimizer, scheduler, scaler, batch, train_iters, max_disp
     split-precision overflow gate; the schedule still advances, as under GradScaler).
     `phase`: "all" (default) | "grads" (zero_grad .. unscaled gradients; returns (loss, metrics)) | "update" (clip .. scheduler
     on the gradients a "grads" call left; returns None) — the two halves of a step for per-segment graph capture.
+    `supervise_init` (the reference's --supervise_init, train_continuous_IGEV.py:220-221): `batch` is the 6-tuple
+    (image1, image2, hr_coord, hr_disp_gt, scale, low_disp_gt [B,h/4,w/4]), the model must return (init_disp, preds) and the loss
+    is sequence_loss_multiscale_superinit.
     Model-agnostic host logic (any module with the reference's forward signature)."""
     loss = metrics = None
     if phase in ("all", "grads"):
-        image1, image2, hr_coord, hr_disp_gt, scale = batch
+        want = 6 if supervise_init else 5
+        if len(batch) != want:
+            raise ValueError(f"train_step: supervise_init={bool(supervise_init)} takes a {want}-tuple batch "
+                             f"(image1, image2, hr_coord, hr_disp_gt, scale{', low_disp_gt' if supervise_init else ''}), got {len(batch)}")
+        image1, image2, hr_coord, hr_disp_gt, scale = batch[:5]
         optimizer.zero_grad()
         assert model.training
         res = model(image1, image2, iters=train_iters, hr_coord=hr_coord, scale=scale)
         disp_preds = res[1] if isinstance(res, tuple) else res  # IGEV: (init_disp, preds); RAFT: preds (prune_raft_stereo.py:297)
-        loss, metrics = sequence_loss_multiscale(disp_preds, hr_disp_gt, (hr_disp_gt < 512) & (hr_disp_gt > 0.0), max_disp=max_disp,
-                                                 sync_free=sync_free_loss)
+        valid = (hr_disp_gt < 512) & (hr_disp_gt > 0.0)
+        if supervise_init:
+            if not isinstance(res, tuple):
+                raise ValueError("train_step: supervise_init needs a model that returns (init_disp, preds); this one returns the "
+                                 "predictions only (RAFT has no init_disp: prune_raft_stereo.py:297)")
+            loss, metrics = sequence_loss_multiscale_superinit(res[0], batch[5], disp_preds, hr_disp_gt, valid, max_disp=max_disp,
+                                                               sync_free=sync_free_loss)
+        else:
+            loss, metrics = sequence_loss_multiscale(disp_preds, hr_disp_gt, valid, max_disp=max_disp, sync_free=sync_free_loss)
         if scaler is not None:
             scaler.scale(loss).backward()
             scaler.unscale_(optimizer)

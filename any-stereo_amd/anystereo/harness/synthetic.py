@@ -90,3 +90,16 @@ def tiny_train_case(name: str):
     coord = torch.stack([grid[i] for i in idx]).contiguous()
     gt = det_uniform((2, 1, nq), 310, 0.5, 40.0)
     return h, w, img1, img2, coord, gt, torch.tensor([[s], [s]])
+
+
+def tiny_low_disp_gt():
+    """low_disp_gt [2,16,32] of the IGEV G8 case (tiny_train_case("igev"): 64x128 input, init_disp at 1/4): the target of the
+    --supervise_init loss (train_continuous_IGEV.py:96-122, stereo_datasets.py:151-156).  U(-1, 40): a few values <= 0, which the
+    reference counts as valid.  The same ~15 % of positions in BOTH samples lie at or above max_disp / 4 = 48 (one of them inf, as
+    Middlebury ground truth holds) and are masked, so both samples have the same number of valid pixels: the mean of the
+    per-sample means is the full-batch mean."""
+    gt = det_uniform((2, 16, 32), 320, -1.0, 40.0)
+    masked = (det_uniform((16, 32), 321, 0.0, 1.0) > 0.85).expand(2, 16, 32)
+    gt = torch.where(masked, det_uniform((2, 16, 32), 322, 48.0, 70.0), gt)
+    gt[:, 0, 0] = float("inf")  # masked in both samples
+    return gt.contiguous()

@@ -20,10 +20,12 @@ from .synthetic import det_uniform, synthetic_pair
 
 
 def synthetic_train_batch(batch: int, height: int = 160, width: int = 320, n_query: int | None = None, seed: int = 0,
-                          scale_min: float = 1.0, scale_max: float = 2.95, device="cpu"):
+                          scale_min: float = 1.0, scale_max: float = 2.95, device="cpu", low_disp: bool = False):
     """(image1, image2, hr_coord [B,Q,2], hr_disp [B,1,Q], scale [B,1]) — Q = height*width by default
     (`sample_q = inp_size[0]*inp_size[1]`, stereo_datasets.py:71), queries drawn without replacement from the
-    cell-centre grid of the round(size*scale) HR image (stereo_datasets.py:190-193)."""
+    cell-centre grid of the round(size*scale) HR image (stereo_datasets.py:190-193).
+    low_disp=True appends low_disp_gt [B, height//4, width//4] (stereo_datasets.py:151-156,212; the target of --supervise_init):
+    U(0.5, 56), so ~14 % of it lies at or above max_disp / 4 = 48 (max_disp 192) and is masked by the loss."""
     q = n_query or height * width
     img1, img2 = synthetic_pair(batch, height, width, shift=8, seed=1000 + seed)
     scale = det_uniform((batch, 1), 2000 + seed, scale_min, scale_max)
@@ -37,7 +39,10 @@ def synthetic_train_batch(batch: int, height: int = 160, width: int = 320, n_que
         rows.append(grid[idx])
     hr_coord = torch.stack(rows).contiguous()
     hr_disp = det_uniform((batch, 1, q), 4000 + seed, 0.5, 64.0)
-    return tuple(t.to(device) for t in (img1, img2, hr_coord, hr_disp, scale))
+    out = (img1, img2, hr_coord, hr_disp, scale)
+    if low_disp:
+        out = out + (det_uniform((batch, height // 4, width // 4), 5000 + seed, 0.5, 56.0),)
+    return tuple(t.to(device) for t in out)
 
 
 def shard_batch(batch, rank: int, world: int):
@@ -62,15 +67,21 @@ class Trainer:
     AdamW simply skips them.  The reducer must not wait for them: the FIRST step therefore runs forward + backward once on the
     bare module, freezes (`requires_grad_(False)`) every parameter that came back without a gradient, and only then wraps the
     module — a plain DDP whose autograd graph is the same every step, with no per-step graph walk (find_unused_parameters cost
-    10 ms of a 129 ms step in round 1) and no dependence on `static_graph`."""
+    10 ms of a 129 ms step in round 1) and no dependence on `static_graph`.
+
+    `supervise_init=True` is the reference's --supervise_init (train_continuous_IGEV.py:220-221): batches are 6-tuples ending in
+    low_disp_gt, the loss is sequence_loss_multiscale_superinit on every path (eager, flat, graphed, the DDP probe), so the
+    classifier receives a gradient and the probe does not freeze it."""
 
     def __init__(self, model, lr: float = 2e-4, wdecay: float = 1e-5, num_steps: int = 100000, train_iters: int = 16,
                  max_disp: int = 192, lr_fixed: bool = False, mixed_precision: bool = False, bucket_cap_mb: int | None = None,
-                 force_ddp: bool = False, loss_scale: float | None = None, graph: bool | None = None, ddp_impl: str | None = None):
+                 force_ddp: bool = False, loss_scale: float | None = None, graph: bool | None = None, ddp_impl: str | None = None,
+                 supervise_init: bool = False):
         model.train()
         model.freeze_bn()  # train_continuous_IGEV.py:203
         self.model = model
         self.module = model
+        self.supervise_init = bool(supervise_init)
         self._want_ddp = td.is_available() and td.is_initialized() and (td.get_world_size() > 1 or force_ddp)
         self._bucket_cap_mb = int(os.environ.get("ANYSTEREO_DDP_BUCKET_MB", "25")) if bucket_cap_mb is None else bucket_cap_mb
         self.ddp_mode = "none"
@@ -171,7 +182,7 @@ class Trainer:
 
     def _wrap_ddp(self, batch):
         """Probe pass on the bare module -> freeze gradient-less parameters -> wrap (see the class docstring)."""
-        from .metrics import sequence_loss_multiscale
+        from .metrics import sequence_loss_multiscale, sequence_loss_multiscale_superinit
         model = self.model
         mode = os.environ.get("ANYSTEREO_DDP", "probe")  # probe (default) | find_unused | static
         if mode == "probe":
@@ -180,10 +191,18 @@ class Trainer:
             model.freeze_bn()
             self._requires_grad_before = {n: p.requires_grad for n, p in model.named_parameters()}
             model.zero_grad(set_to_none=True)
-            image1, image2, hr_coord, gt, scale = batch
+            if len(batch) != (6 if self.supervise_init else 5):
+                raise ValueError(f"Trainer: supervise_init={self.supervise_init} takes {6 if self.supervise_init else 5}-tuple batches, "
+                                 f"got {len(batch)}")
+            image1, image2, hr_coord, gt, scale = batch[:5]
             res = model(image1, image2, iters=min(2, self.train_iters), hr_coord=hr_coord.clone(), scale=scale)
             preds = res[1] if isinstance(res, tuple) else res
-            loss, _ = sequence_loss_multiscale(preds, gt, (gt < 512) & (gt > 0.0), max_disp=self.max_disp)
+            if self.supervise_init:  # the loss of the run: init_disp is supervised, so the classifier keeps its gradient
+                if not isinstance(res, tuple):
+                    raise ValueError("Trainer: supervise_init needs a model that returns (init_disp, preds)")
+                loss, _ = sequence_loss_multiscale_superinit(res[0], batch[5], preds, gt, (gt < 512) & (gt > 0.0), max_disp=self.max_disp)
+            else:
+                loss, _ = sequence_loss_multiscale(preds, gt, (gt < 512) & (gt > 0.0), max_disp=self.max_disp)
             loss.backward()
             for n, p in model.named_parameters():
                 if p.requires_grad and p.grad is None:
@@ -247,7 +266,8 @@ class Trainer:
             return self._step_flat(batch, sync_grads)
         watch = (self.loss_scale != 1.0 or self.overflow_events) and self.overflow_policy != "off" and self._on_gpu()
         gate = self._overflow_gate if (watch and self.overflow_policy == "skip") else None
-        kw = dict(max_disp=self.max_disp, loss_scale=self.loss_scale, sync_free_loss=self.sync_free_loss, should_step=gate)
+        kw = dict(max_disp=self.max_disp, loss_scale=self.loss_scale, sync_free_loss=self.sync_free_loss, should_step=gate,
+                  supervise_init=self.supervise_init)
         if not sync_grads and self.module is not self.model:
             with self.module.no_sync():
                 out = train_step(self.module, self.optimizer, self.scheduler, self.scaler, batch, self.train_iters, **kw)
@@ -277,7 +297,7 @@ class Trainer:
         watch = (self.loss_scale != 1.0 or self.overflow_events) and self.overflow_policy != "off" and self._on_gpu()
         gate = self._overflow_gate if (watch and self.overflow_policy == "skip") else None
         out = train_step(self.model, self.optimizer, None, self.scaler, batch, self.train_iters, max_disp=self.max_disp,
-                         loss_scale=self.loss_scale, sync_free_loss=self.sync_free_loss, phase="grads")
+                         loss_scale=self.loss_scale, sync_free_loss=self.sync_free_loss, phase="grads", supervise_init=self.supervise_init)
         if sync_grads:
             self.allreduce_gradients_flat()
             if self.scaler is not None and td.get_world_size() > 1:
@@ -329,10 +349,10 @@ class Trainer:
                 with torch.autograd.set_multithreading_enabled(not single), torch.cuda.stream(self._gstream):
                     if self._want_ddp:  # the ranks stay in step during the warm-up too
                         out = train_step(self.module, self.optimizer, None, None, batch, self.train_iters, max_disp=self.max_disp,
-                                         loss_scale=self.loss_scale, sync_free_loss=True, phase="grads")
+                                         loss_scale=self.loss_scale, sync_free_loss=True, phase="grads", supervise_init=self.supervise_init)
                     else:
                         out = train_step(self.module, self.optimizer, self.scheduler, None, batch, self.train_iters, max_disp=self.max_disp,
-                                         loss_scale=self.loss_scale, sync_free_loss=True)
+                                         loss_scale=self.loss_scale, sync_free_loss=True, supervise_init=self.supervise_init)
                 if self._want_ddp:
                     # the collective is issued from the CALLER's stream, as after a replay: the process group records its
                     # synchronisation events on the issuing stream, and its watchdog thread may not query an event whose last
@@ -367,7 +387,7 @@ class Trainer:
             with torch.autograd.set_multithreading_enabled(not single), torch.cuda.graph(g, stream=self._gstream, capture_error_mode=mode):
                 loss, metrics = train_step(self.module, self.optimizer, None, None, static, self.train_iters, max_disp=self.max_disp,
                                            loss_scale=self.loss_scale, sync_free_loss=True,
-                                           phase="all" if self.graph_scope == "step" else "grads")
+                                           phase="all" if self.graph_scope == "step" else "grads", supervise_init=self.supervise_init)
             # Memset nodes (ATen's reduction semaphores, MIOpen's split-K zero-fills: 34 in the IGEV step) -> fill kernel nodes.  Inside
             # a chain this long the runtime does not reliably order them with the kernels around them: from the second replay on
             # the reductions behind them returned stale values (valid-pixel count, metrics) and gradients came back zero

@@ -238,9 +238,15 @@ class continuous_IGEVStereo(ContinuousStereoBase):
             geo_encoding_volume = self.cost_agg(gwc_volume, features_left)
             if B.fused_ok(geo_encoding_volume, self) and B.conv3d_k3_ok(self.classifier):
                 cost = B.conv3d_fused(self, self.classifier, None, geo_encoding_volume, 0)
+                init_disp = self._hot_init_disp(cost.squeeze(1))
+            elif (B.init_head_ok(self.classifier, geo_encoding_volume)
+                  and type(self)._hot_init_disp is continuous_IGEVStereo._hot_init_disp):
+                # training on the GPU: the same forward kernels, and a fused backward for a loss that differentiates init_disp
+                # (train_continuous_IGEV.py:96-122, --supervise_init); the default loss never reaches it (the loop detaches disp)
+                init_disp = G.InitDispHead.apply(geo_encoding_volume, self.classifier.weight)
             else:
                 cost = B.conv3d_train(self.classifier, geo_encoding_volume)
-            init_disp = self._hot_init_disp(cost.squeeze(1))
+                init_disp = self._hot_init_disp(cost.squeeze(1))
             self._mark("cost_agg_end")
             del gwc_volume
             if side is None:

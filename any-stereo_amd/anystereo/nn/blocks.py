@@ -159,6 +159,42 @@ def conv3d_fused(mod: nn.Module, conv: nn.Conv3d, bn, x: torch.Tensor, act: int,
     return ops.conv3d_k3(x.contiguous(), w, b, conv.stride[0], act, gate=None if gate is None else gate.contiguous())
 
 
+def searched_conv_forward(x, w, bias, cfg):
+    """aten.convolution with MIOpen's solver search on (see _SearchedConv) -> (y, x, w) with x, w as the convolution consumed them.
+    Under autocast (the reference's training arithmetic, train_continuous_IGEV.py:206) the convolution runs in the autocast
+    dtype, as nn.Conv3d would: operands are cast HERE (aten.convolution called directly would be cast by autocast's own
+    wrapper, but the tensors saved for backward would keep their dtypes and convolution_backward refuses a mix); the callers
+    return their gradients in the dtypes the inputs came in."""
+    if torch.is_autocast_enabled("cuda"):
+        dt = torch.get_autocast_dtype("cuda")
+        x, w, bias = x.to(dt), w.to(dt), (None if bias is None else bias.to(dt))
+    elif x.dtype != w.dtype:
+        x = x.to(w.dtype)
+    prev = torch.backends.cudnn.benchmark
+    torch.backends.cudnn.benchmark = True
+    try:
+        with torch.autocast("cuda", enabled=False):
+            return torch.ops.aten.convolution(x, w, bias, *cfg), x, w
+    finally:
+        torch.backends.cudnn.benchmark = prev
+
+
+def conv3d_cfg(conv):
+    """aten.convolution's (stride, padding, dilation, transposed, output_padding, groups) of an nn.Conv3d / nn.ConvTranspose3d."""
+    transposed = isinstance(conv, nn.ConvTranspose3d)
+    return (list(conv.stride), list(conv.padding), list(conv.dilation), transposed,
+            list(conv.output_padding) if transposed else [0, 0, 0], conv.groups)
+
+
+def init_head_ok(conv: nn.Module, x: torch.Tensor) -> bool:
+    """The classifier + softmax + regression of the IGEV init-disparity head (continuous_IGEVstereo.py:267-268) in training on
+    the GPU has a fused HIP backward (grad.InitDispHead): Conv3d(8 -> 1, 3x3x3, padding 1, stride 1, no bias) and D <= 128."""
+    return (x.is_cuda and x.dim() == 5 and torch.is_grad_enabled() and (x.requires_grad or conv.weight.requires_grad)
+            and not _NO_SEARCHED_CONV and isinstance(conv, nn.Conv3d) and conv.kernel_size == (3, 3, 3) and conv.padding == (1, 1, 1)
+            and conv.stride == (1, 1, 1) and conv.dilation == (1, 1, 1) and conv.groups == 1 and conv.in_channels == 8
+            and conv.out_channels == 1 and conv.bias is None and x.shape[1] == 8 and 1 <= x.shape[2] <= ops.INIT_HEAD_MAX_D)
+
+
 class _SearchedConv(torch.autograd.Function):
     """aten.convolution / convolution_backward with MIOpen's solver SEARCH enabled for these calls only.
     Without a tuning database MIOpen's immediate mode serves the hourglass' 3-D convolutions (17 configurations) with
@@ -167,25 +203,11 @@ class _SearchedConv(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w, bias, cfg):
-        # Under autocast (the reference's training arithmetic, train_continuous_IGEV.py:206) the convolution runs in the autocast
-        # dtype, as nn.Conv3d would: operands are cast HERE (aten.convolution called directly would be cast by autocast's own
-        # wrapper, but the tensors saved for backward would keep their dtypes and convolution_backward refuses a mix); the
-        # gradients go back in the dtypes the inputs came in.
         ctx.in_dtypes = (x.dtype, w.dtype, None if bias is None else bias.dtype)
-        if torch.is_autocast_enabled("cuda"):
-            dt = torch.get_autocast_dtype("cuda")
-            x, w, bias = x.to(dt), w.to(dt), (None if bias is None else bias.to(dt))
-        elif x.dtype != w.dtype:
-            x = x.to(w.dtype)
+        y, x, w = searched_conv_forward(x, w, bias, cfg)
         ctx.save_for_backward(x, w)
         ctx.cfg, ctx.bias_sizes = cfg, None if bias is None else list(bias.shape)
-        prev = torch.backends.cudnn.benchmark
-        torch.backends.cudnn.benchmark = True
-        try:
-            with torch.autocast("cuda", enabled=False):
-                return torch.ops.aten.convolution(x, w, bias, *cfg)
-        finally:
-            torch.backends.cudnn.benchmark = prev
+        return y
 
     @staticmethod
     def backward(ctx, gy):
@@ -209,10 +231,7 @@ def conv3d_train(conv, x):
         return conv(x)
     if _NO_SEARCHED_CONV:  # diagnostics: MIOpen's immediate mode (naive kernels) instead of the searched solvers
         return conv(x)
-    transposed = isinstance(conv, nn.ConvTranspose3d)
-    cfg = (list(conv.stride), list(conv.padding), list(conv.dilation), transposed,
-           list(conv.output_padding) if transposed else [0, 0, 0], conv.groups)
-    return _SearchedConv.apply(x, conv.weight, conv.bias, cfg)
+    return _SearchedConv.apply(x, conv.weight, conv.bias, conv3d_cfg(conv))
 
 
 def _conv_nd(is_3d: bool, deconv: bool):

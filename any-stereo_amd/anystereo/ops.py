@@ -359,6 +359,34 @@ def disparity_regression(cost: torch.Tensor, apply_softmax: bool) -> torch.Tenso
     return out
 
 
+INIT_HEAD_MAX_D = 128  # as_init_head_bwd serves 1 <= D <= 128 (max_disp <= 512)
+
+
+def init_head_bwd(geo: torch.Tensor, weight: torch.Tensor, cost: torch.Tensor, g: torch.Tensor):
+    """Backward of classifier Conv3d(8 -> 1, 3x3x3, padding 1, no bias) + softmax over D + disparity regression
+    (continuous_IGEVstereo.py:267-268, submodule.py:321-325) -> (d_geo [B,8,D,H,W], d_weight [1,8,3,3,3]).
+    geo [B,8,D,H,W], weight [1,8,3,3,3], cost [B,D,H,W] (the classifier's output), g [B,H,W] or [B,1,H,W] = dL/d init_disp;
+    all fp32.  Two launches: d_geo + per-block weight-gradient partials, then their sum in a fixed order (deterministic)."""
+    _req(geo, "geo"), _req(weight, "weight"), _req(cost, "cost"), _req(g, "g")
+    if geo.dim() != 5 or geo.shape[1] != 8 or tuple(weight.shape) != (1, 8, 3, 3, 3):
+        raise RuntimeError(f"init_head_bwd: geo [B,8,D,H,W] and weight [1,8,3,3,3] expected, got {tuple(geo.shape)}, {tuple(weight.shape)}")
+    b, _, d, h, w = geo.shape
+    if tuple(cost.shape) != (b, d, h, w) or g.numel() != b * h * w:
+        raise RuntimeError(f"init_head_bwd: cost {tuple(cost.shape)} / g {tuple(g.shape)} do not match geo {tuple(geo.shape)}")
+    lib = L.load()
+    n = lib.as_init_head_partial_elems(b, h, w)
+    if n <= 0:
+        L.check(int(n), "init_head_partial_elems")
+    d_geo = torch.empty_like(geo)
+    partial = torch.empty((n,), device=geo.device, dtype=torch.float32)
+    d_w = torch.empty((1, 8, 3, 3, 3), device=geo.device, dtype=torch.float32)
+    with _guard(geo.device):
+        L.check(lib.as_init_head_bwd(_p(geo), _p(weight), _p(cost), _p(g), _p(d_geo), _p(partial), b, d, h, w, _stream()),
+                "init_head_bwd")
+        L.check(lib.as_init_head_wgrad_reduce(_p(partial), n // 216, _p(d_w), _stream()), "init_head_wgrad_reduce")
+    return d_geo, d_w
+
+
 # ------------------------------------------------------------------------------------------------
 # convolutions (update block, MLP)
 # ------------------------------------------------------------------------------------------------

@@ -488,6 +488,18 @@ int as_gwc_volume_bwd(const float* fl, const float* fr, const float* d_vol, floa
                       int B, int C, int H, int W, int D, int G, void* stream);
 int as_disparity_regression_bwd(const float* cost, const float* d_out, float* d_cost, int B, int D, int H, int W,
                                 int apply_softmax, void* stream);
+/*   a5'^T init-disparity head backward — replaces autograd through the classifier Conv3d(8->1, 3x3x3, padding 1, no bias), F.softmax
+ *         and disparity_regression (continuous_IGEVstereo.py:267-268, submodule.py:321-325) when the loss of
+ *         train_continuous_IGEV.py:96-122,220-221 (--supervise_init) differentiates init_disp.
+ *         geo [B,8,D,H,W], weight [1,8,3,3,3], cost [B,D,H,W] (the classifier's output, the forward's softmax input), g [B,H,W] =
+ *         dL/d init_disp -> d_geo [B,8,D,H,W] (written in full) and partial [as_init_head_partial_elems(B,H,W)] = one row of 216
+ *         weight-gradient partial sums per block (written in full); 1 <= D <= 128 (max_disp <= 512), AS_ERR_BAD_SHAPE otherwise.
+ *         as_init_head_wgrad_reduce sums the `nrows` = elems / 216 rows in a fixed order into d_weight [1,8,3,3,3] (overwritten).
+ *         No atomics, no zero-fill: the same bits on every run. */
+int64_t as_init_head_partial_elems(int B, int H, int W);
+int as_init_head_bwd(const float* geo, const float* weight, const float* cost, const float* g, float* d_geo, float* partial, int B,
+                     int D, int H, int W, void* stream);
+int as_init_head_wgrad_reduce(const float* partial, int nrows, float* d_weight, void* stream);
 int as_liif_gather_bwd(const float* d_latent, const float* coord, float* d_feat,
                        int B, int C, int H, int W, int Q, int lat_ctot, int lat_coff, void* stream);
 /* deterministic form (no atomics): `order` [B,Q] = the queries of each batch element stably sorted by source pixel, `starts`
