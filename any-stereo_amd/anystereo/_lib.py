@@ -155,6 +155,9 @@ SIGNATURES = {
     "as_gru_gates_q_bwd_ctx": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "as_liif_rel_key": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp]),
     "as_convex_upsample_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "as_disp_metrics_partial_elems": (C.c_int64, [_i, _i, _i, _i]),
+    "as_disp_metrics": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i] + [C.c_float] * 5 + [_vp]),
+    "as_lr_consistency": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
 }
 
 _lib = None

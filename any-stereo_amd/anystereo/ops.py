@@ -388,6 +388,88 @@ def init_head_bwd(geo: torch.Tensor, weight: torch.Tensor, cost: torch.Tensor, g
 
 
 # ------------------------------------------------------------------------------------------------
+# evaluation: fused disparity metrics and the left-right-consistency mask (csrc/eval_metrics.hip)
+# ------------------------------------------------------------------------------------------------
+
+METRIC_ROW = 19  # all | noc | occ: (n, sum E, n_D1, n_T1, n_T2, n_T3), then n_gt_pos
+
+
+def _req_mask(t: Optional[torch.Tensor], name: str, shape) -> Optional[torch.Tensor]:
+    """A uint8 or bool mask of `shape` (None = all ones) -> uint8 view."""
+    if t is None:
+        return None
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA (HIP) tensor — the anystereo hot path has no CPU fallback")
+    if t.dtype not in (torch.uint8, torch.bool):
+        raise RuntimeError(f"{name} must be uint8 or bool, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+    if tuple(t.shape) != tuple(shape):
+        raise RuntimeError(f"{name} {tuple(t.shape)} does not match gt {tuple(shape)}")
+    return t.view(torch.uint8) if t.dtype == torch.bool else t
+
+
+def disparity_metrics(est: torch.Tensor, gt: torch.Tensor, valid: Optional[torch.Tensor] = None, noc: Optional[torch.Tensor] = None,
+                      gt_lo: float = float("-inf"), gt_hi: float = float("inf"), thres=(1.0, 2.0, 3.0),
+                      out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """EPE / D1 / Thres sums of N estimates against one ground truth in one pass (evaluation.py:389-417, metrics.py:66-118).
+    est fp32 [N,B,H,W] (or [B,H,W] = one estimate), gt fp32 [B,H,W], valid / noc uint8 or bool [B,H,W] or None (= all ones).
+    -> fp64 [N,B,19] on the device: per region all, noc = valid & noc, occ = valid & ~noc the six numbers
+    (n, sum |gt - est|, n_D1, n_Thres1, n_Thres2, n_Thres3), then n_gt_pos = #(gt > 0).  A pixel is valid when its mask is set and
+    gt_lo < gt < gt_hi; an estimate of +-inf counts as 0.  No synchronisation; the same bits on every call.
+    `out` (optional, fp64 [N,B,19] contiguous) receives the result: every element is written."""
+    _req(est, "est"), _req(gt, "gt")
+    if gt.dim() != 3:
+        raise RuntimeError(f"disparity_metrics: gt must be [B,H,W], got {tuple(gt.shape)}")
+    if est.dim() == 3:
+        est = est.unsqueeze(0)
+    if est.dim() != 4 or tuple(est.shape[1:]) != tuple(gt.shape):
+        raise RuntimeError(f"disparity_metrics: est {tuple(est.shape)} does not match gt {tuple(gt.shape)} ([N,B,H,W] against [B,H,W])")
+    n, b, h, w = est.shape
+    if n < 1 or b < 1 or h < 1 or w < 1:
+        raise RuntimeError(f"disparity_metrics: empty input {tuple(est.shape)}")
+    valid, noc = _req_mask(valid, "valid", gt.shape), _req_mask(noc, "noc", gt.shape)
+    if len(thres) != 3:
+        raise RuntimeError(f"disparity_metrics: three thresholds expected, got {len(thres)}")
+    lib = L.load()
+    elems = lib.as_disp_metrics_partial_elems(n, b, h, w)
+    if elems <= 0:
+        L.check(int(elems), "disp_metrics_partial_elems")
+    if out is None:
+        out = torch.empty((n, b, METRIC_ROW), device=est.device, dtype=torch.float64)
+    else:
+        _req(out, "out", torch.float64)
+        if tuple(out.shape) != (n, b, METRIC_ROW) or out.device != est.device:
+            raise RuntimeError(f"disparity_metrics: out must be {(n, b, METRIC_ROW)} on {est.device}, got {tuple(out.shape)} on {out.device}")
+    partial = torch.empty((elems,), device=est.device, dtype=torch.float64)
+    with _guard(est.device):
+        L.check(lib.as_disp_metrics(_p(est), _p(gt), _p(valid), _p(noc), _p(partial), _p(out), n, b, h, w, float(gt_lo), float(gt_hi),
+                                    float(thres[0]), float(thres[1]), float(thres[2]), _stream()), "disp_metrics")
+    return out
+
+
+def lr_consistency(dl: torch.Tensor, dr: torch.Tensor, thr: float = 3.0) -> torch.Tensor:
+    """The non-occluded mask of occ_mask(left_disp, right_disp) (experiment.py:286-296): uint8 [B,H,W], 1 where the column index
+    warped left -> right -> left lands within `thr` px of itself.  dl, dr fp32 [B,H,W] (or [B,1,H,W]), H, W >= 2."""
+    _req(dl, "dl"), _req(dr, "dr")
+    if dl.dim() == 4 and dl.shape[1] == 1:
+        dl = dl[:, 0]
+    if dr.dim() == 4 and dr.shape[1] == 1:
+        dr = dr[:, 0]
+    if dl.dim() != 3 or dl.shape != dr.shape:
+        raise RuntimeError(f"lr_consistency: dl {tuple(dl.shape)} and dr {tuple(dr.shape)} must share a [B,H,W] shape")
+    b, h, w = dl.shape
+    if b < 1 or h < 2 or w < 2:
+        raise RuntimeError(f"lr_consistency: needs B >= 1 and H, W >= 2, got {tuple(dl.shape)}")
+    noc = torch.empty((b, h, w), device=dl.device, dtype=torch.uint8)
+    with _guard(dl.device):
+        L.check(L.load().as_lr_consistency(_p(dl), _p(dr), _p(noc), b, h, w, float(thr), _stream()), "lr_consistency")
+    return noc
+
+
+# ------------------------------------------------------------------------------------------------
 # convolutions (update block, MLP)
 # ------------------------------------------------------------------------------------------------
 

@@ -15,6 +15,8 @@ Stateless operators (reference call site):
     structure_feature(x) -> Tensor                                       liif.py:432-446, :496-499
     convex_upsample(disp, mask, coord, scale?, mask_is_logits) -> Tensor submodule.py:357-372
     corr_sampler_forward / corr_sampler_backward                         sampler/sampler.cpp:24-45
+    disparity_metrics(est, gt, valid?, noc?, gt_lo, gt_hi, thres) -> Tensor  evaluation.py:389-417, metrics.py:66-118 -> fp64 [N,B,19]
+    lr_consistency(dl, dr, thr) -> Tensor                                experiment.py:286-296 -> uint8 [B,H,W]
 Operators that carry weights take them as tensors, in the reference module's parameter order:
     motion_encoder(disp, corr, weights[5], biases[5]) -> Tensor          update.py:84-92  (convc1, convc2, convd1, convd2, conv)
     convgru_step(h, cz, cr, cq, x[], weights[3], biases[3]) -> Tensor    update.py:33-41  (convz, convr, convq)
@@ -43,6 +45,8 @@ _lib.define("structure_feature(Tensor x) -> Tensor")
 _lib.define("convex_upsample(Tensor disp, Tensor mask, Tensor coord, Tensor? scale, bool mask_is_logits) -> Tensor")
 _lib.define("corr_sampler_forward(Tensor volume, Tensor coords, int radius) -> Tensor")
 _lib.define("corr_sampler_backward(Tensor volume, Tensor coords, Tensor corr_grad, int radius) -> Tensor")
+_lib.define("disparity_metrics(Tensor est, Tensor gt, Tensor? valid, Tensor? noc, float gt_lo, float gt_hi, float[] thres) -> Tensor")
+_lib.define("lr_consistency(Tensor dl, Tensor dr, float thr) -> Tensor")
 _lib.define("motion_encoder(Tensor disp, Tensor corr, Tensor[] weights, Tensor[] biases) -> Tensor")
 _lib.define("convgru_step(Tensor h, Tensor cz, Tensor cr, Tensor cq, Tensor[] x, Tensor[] weights, Tensor[] biases) -> Tensor")
 _lib.define("disp_head(Tensor x, Tensor[] weights, Tensor[] biases) -> Tensor")
@@ -50,7 +54,7 @@ _lib.define("liif_upsample(Tensor[] feats, Tensor coord, Tensor[] weights, Tenso
 
 OPS = ("corr_build_pyramid", "geo_pyramid", "geo_corr_lookup", "gwc_volume", "disparity_regression", "structure_feature",
        "convex_upsample", "corr_sampler_forward", "corr_sampler_backward", "motion_encoder", "convgru_step", "disp_head",
-       "liif_upsample")
+       "liif_upsample", "disparity_metrics", "lr_consistency")
 
 
 def _f(t: torch.Tensor) -> torch.Tensor:
@@ -115,6 +119,14 @@ def _corr_sampler_forward(volume, coords, radius):
 
 def _corr_sampler_backward(volume, coords, corr_grad, radius):
     return ops.corr_sampler_backward(volume, coords, corr_grad, radius)
+
+
+def _disparity_metrics(est, gt, valid, noc, gt_lo, gt_hi, thres):
+    return ops.disparity_metrics(est, gt, valid, noc, gt_lo, gt_hi, tuple(thres))
+
+
+def _lr_consistency(dl, dr, thr):
+    return ops.lr_consistency(dl, dr, thr)
 
 
 # ---- operators with weights: the models' own nn modules, called with the caller's tensors as parameters ----------
@@ -199,6 +211,7 @@ _IMPLS = {
     "convex_upsample": _convex_upsample, "corr_sampler_forward": _corr_sampler_forward,
     "corr_sampler_backward": _corr_sampler_backward, "motion_encoder": _motion_encoder, "convgru_step": _convgru_step,
     "disp_head": _disp_head, "liif_upsample": _liif_upsample,
+    "disparity_metrics": _disparity_metrics, "lr_consistency": _lr_consistency,
 }
 for _name, _fn in _IMPLS.items():
     _lib.impl(_name, _fn, "CUDA")

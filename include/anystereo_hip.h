@@ -583,6 +583,32 @@ int as_conv7x7_c3(const float* x, const void* wpack, const float* bias, float* o
 int as_conv3x3_few(const float* x, const float* wpack, const float* bias, float* out, int B, int Cin, int Cout, int H, int W,
                    int stride, int act, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * On-device evaluation (csrc/eval_metrics.hip)
+ *
+ * as_disp_metrics  replaces the 45 per-image metric calls of evaluation.py:399-417 (EPE / D1 / Thres-1,2,3 of
+ *                  metrics_utils/metrics.py:66-118 over the regions all, non-occluded, occluded), the inf -> 0 rule of
+ *                  evaluation.py:389 and the mask arithmetic of :391-395 with one pass over the prediction.
+ *                  est [N,B,H,W] = N estimates of the same images, gt [B,H,W], valid / noc uint8 [B,H,W] or NULL (= all ones;
+ *                  noc: 1 = non-occluded).  A pixel counts when valid != 0 && gt > gt_lo && gt < gt_hi (-inf / +inf disable the
+ *                  bounds: `disp_gt < 1000`, --max_enable).  E = |gt - est| in fp32, an estimate of +-inf counts as 0, NaN
+ *                  propagates.  out [N,B,19] fp64 (written in full), per (estimate, image):
+ *                    [ all: n, sum E, n_D1, n_T1, n_T2, n_T3 | noc = valid & noc: the same six | occ = valid & !noc: the same six |
+ *                      n_gt_pos ]
+ *                  D1 = E > 3 && E / |gt| > 0.05 (IEEE fp32 division), Tk = E > thres_k, n_gt_pos = #(gt > 0) over the whole image
+ *                  (the denominator of the `_filter` rule, metrics.py:53).  Counts are exact, sum E accumulates in fp64.
+ *                  partial = as_disp_metrics_partial_elems doubles of scratch (written in full): one row per 2048-pixel chunk,
+ *                  summed by a second launch in a fixed order.  No atomics, no zero-fill: the same bits on every run; an empty
+ *                  region gives zeros.
+ * as_lr_consistency  replaces occ_mask (metrics_utils/experiment.py:286-296, used at evaluation.py:394) and its two warp calls
+ *                  (:267-284): noc [B,H,W] uint8 = 1 where |x - l2r2l(x)| < thr for left / right disparities dl, dr [B,H,W]; no
+ *                  intermediate image.  H < 2 or W < 2: AS_ERR_BAD_SHAPE (the base grid divides by n - 1). */
+int64_t as_disp_metrics_partial_elems(int N, int B, int H, int W);
+int as_disp_metrics(const float* est, const float* gt, const unsigned char* valid, const unsigned char* noc, double* partial,
+                    double* out, int N, int B, int H, int W, float gt_lo, float gt_hi, float thres1, float thres2, float thres3,
+                    void* stream);
+int as_lr_consistency(const float* dl, const float* dr, unsigned char* noc, int B, int H, int W, float thr, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

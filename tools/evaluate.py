@@ -1,0 +1,86 @@
+"""The evaluation protocol (anystereo/harness/evaluate.py) over synthetic pairs whose ground truth is known: `synthetic_pair(shift=k)`
+has disparity k everywhere, so the right view's ground truth is k as well.  One JSON line on stdout (rank 0).
+
+    python tools/evaluate.py --pairs 8 --height 256 --width 512 --scale 1.5 --iters 8 --protocol things
+    python -m torch.distributed.run --nproc-per-node 2 tools/evaluate.py --pairs 8       # pairs sharded over the ranks
+
+The weights are the deterministic fill, so EPE here says nothing about a trained model: the
+line shows that the protocol runs on the device, what it counts and how fast.  No dataset readers.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
+sys.path[:0] = [ROOT, os.path.join(ROOT, "any-stereo_amd")]
+
+import torch  # noqa: E402
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--model", default="continuous_IGEVStereo", choices=["continuous_IGEVStereo", "continuous_RAFTStereo"])
+    ap.add_argument("--protocol", default="things", choices=["things", "kitti", "middlebury", "eth3d"])
+    ap.add_argument("--pairs", type=int, default=4)
+    ap.add_argument("--height", type=int, default=128)
+    ap.add_argument("--width", type=int, default=256)
+    ap.add_argument("--shift", type=int, default=6)
+    ap.add_argument("--scale", type=float, default=1.5)
+    ap.add_argument("--iters", type=int, default=8)
+    ap.add_argument("--max-disp", type=float, default=None)
+    a = ap.parse_args()
+
+    from anystereo import _lib
+    from anystereo.harness import dist
+    from anystereo.harness.evaluate import Evaluator, evaluate
+    from anystereo.harness.synthetic import fill_module_deterministic, synthetic_pair
+    from anystereo.models import __models__, default_args
+
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/evaluate.py needs a GPU: the models' hot path has no CPU fallback")
+    rank, world, local = dist.env_rank()
+    dev = torch.device("cuda", local % torch.cuda.device_count())
+    torch.cuda.set_device(dev)
+    dist.init("gloo")  # the only traffic is the merge of the per-image rows: a few KB from host memory
+    _lib.load()
+
+    args = default_args(a.model)
+    model = __models__[a.model](args).eval()
+    fill_module_deterministic(model, base_seed=1)
+    model = model.to(dev)
+
+    def pairs():
+        for i in dist.shard_indices(a.pairs, rank, world):
+            i1, i2 = synthetic_pair(1, a.height, a.width, shift=a.shift, seed=1000 + i)
+            gt = torch.full((1, a.height, a.width), float(a.shift), device=dev)
+            valid = torch.ones((1, a.height, a.width), device=dev)
+            extra = gt.clone() if a.protocol == "things" else torch.ones((1, a.height, a.width), dtype=torch.uint8, device=dev)
+            yield i1.to(dev), i2.to(dev), gt, valid, extra
+
+    divis_by = 32 if "IGEV" in a.model else 16
+    evaluate(model, list(pairs())[:1], scale=a.scale, iters=a.iters, protocol=a.protocol, divis_by=divis_by)  # warm-up, not counted
+    ev = Evaluator(a.protocol, max_disp=a.max_disp)
+    res = evaluate(model, pairs(), scale=a.scale, iters=a.iters, protocol=a.protocol, evaluator=ev, divis_by=divis_by)
+    local_rate, local_pairs = res["pairs_per_s"], res["pairs"]
+    if world > 1:
+        ev.merge()
+        merged = ev.result()
+        rates = [0.0] * world
+        rates[rank] = local_rate
+        rates = dist.sum_over_ranks(rates)
+    else:
+        merged, rates = {k: res[k] for k in ("all", "noc", "occ", "images")}, [local_rate]
+    dist.finalize()
+    if rank == 0:
+        print(json.dumps({"tool": "evaluate", "model": a.model, "protocol": a.protocol, "n_gpus": world, "pairs": a.pairs,
+                          "size": [a.height, a.width], "scale": a.scale, "iters": a.iters, "gt_disparity": a.shift,
+                          "weights": "deterministic fill", "pairs_per_s": round(sum(rates), 3),
+                          "per_rank_pairs_per_s": [round(r, 3) for r in rates], "rank0_pairs": local_pairs,
+                          "library": _lib.library_info(), **merged}))
+
+
+if __name__ == "__main__":
+    main()
