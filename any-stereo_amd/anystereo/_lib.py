@@ -158,6 +158,8 @@ SIGNATURES = {
     "as_disp_metrics_partial_elems": (C.c_int64, [_i, _i, _i, _i]),
     "as_disp_metrics": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i] + [C.c_float] * 5 + [_vp]),
     "as_lr_consistency": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
+    "as_prepare_pair": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
+    "as_query_grid": (_i, [_vp] + [_i] * 9 + [_vp]),
 }
 
 _lib = None

@@ -22,7 +22,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import dist
-from .query import pad_for_multi_train
+from .query import pad_for_multi_train, prepare_on_device
 
 REGIONS = ("all", "noc", "occ")
 METRICS = ("EPE", "D1", "Thres1", "Thres2", "Thres3")
@@ -246,7 +246,7 @@ class Evaluator:
 
 @torch.no_grad()
 def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", max_disp: Optional[float] = None, thres=(1, 2, 3),
-             divis_by: int = 32, evaluator: Optional[Evaluator] = None) -> dict:
+             divis_by: int = 32, evaluator: Optional[Evaluator] = None, prep: str = "host") -> dict:
     """Run `model` over `pairs` as the reference's validate_* loops do (evaluation.py:341-373): down-scale by `scale` and pad
     (`query.pad_for_multi_train`), query the full-resolution grid in test_mode, reshape [B,1,Q] -> [B,H,W] and feed an Evaluator.
 
@@ -254,9 +254,13 @@ def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", ma
     gt [B,H,W]; `extra` is the right view's ground truth for "things" and the non-occluded mask for the other protocols.
     Returns the Evaluator's result plus {"pairs", "seconds", "pairs_per_s"}; the host synchronises once, at the end.  `evaluator`:
     feed this one (a rank of a sharded dataset calls its `merge()` afterwards) instead of a new Evaluator(protocol, ...).
+    prep: "host" = `query.pad_for_multi_train` (torch ops, the query grid built on the host and uploaded); "device" =
+    `query.prepare_on_device` (two launches, nothing on the host; the images may be uint8).
 
     Only the last GRU iteration is evaluated: in test_mode the models up-sample the final disparity alone
     (continuous_IGEVstereo.py:267-268), so a per-iteration curve would cost one up-sampling pass per iteration."""
+    if prep not in ("host", "device"):
+        raise ValueError(f"evaluate: prep must be 'host' or 'device', got {prep!r}")
     ev = evaluator if evaluator is not None else Evaluator(protocol, max_disp=max_disp, thres=thres)
     model.eval()
     n_pairs = 0
@@ -265,10 +269,14 @@ def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", ma
         image1, image2, gt, valid = pair[:4]
         extra = pair[4] if len(pair) > 4 else None
         bs, _, h, w = image1.shape
-        i1, i2, coord, _ = pad_for_multi_train(image1, image2, scale, divis_by=divis_by)
-        coord = coord.to(image1.device).unsqueeze(0).expand(bs, *coord.shape).contiguous()
+        if prep == "device":
+            i1, i2, coord, _ = prepare_on_device(image1, image2, scale, divis_by=divis_by)
+        else:
+            i1, i2, coord, _ = pad_for_multi_train(image1, image2, scale, divis_by=divis_by)
+            coord = coord.to(image1.device).unsqueeze(0).expand(bs, *coord.shape).contiguous()
+            i1, i2 = i1.contiguous(), i2.contiguous()
         sc = torch.full((bs, 1), float(scale), device=image1.device)
-        pred = model(i1.contiguous(), i2.contiguous(), iters=iters, test_mode=True, hr_coord=coord, scale=sc)
+        pred = model(i1, i2, iters=iters, test_mode=True, hr_coord=coord, scale=sc)
         est = pred.reshape(1, bs, h, w)
         if ev.protocol == "things":
             ev.update(est, gt, valid, gt_right=extra)

@@ -470,6 +470,70 @@ def lr_consistency(dl: torch.Tensor, dr: torch.Tensor, thr: float = 3.0) -> torc
 
 
 # ------------------------------------------------------------------------------------------------
+# evaluation inputs: bicubic down-scale + replicate pad of the pair, and the query grid (csrc/prepare.hip)
+# ------------------------------------------------------------------------------------------------
+
+def _req_image(t: torch.Tensor, name: str) -> torch.Tensor:
+    if not isinstance(t, torch.Tensor):
+        raise RuntimeError(f"{name}: expected a tensor, got {type(t).__name__}")
+    if not t.is_cuda:
+        raise RuntimeError(f"{name} must be a CUDA (HIP) tensor — the anystereo hot path has no CPU fallback")
+    if t.dtype not in (torch.uint8, torch.float32):
+        raise RuntimeError(f"{name} must be uint8 or float32, got {t.dtype}")
+    if not t.is_contiguous():
+        raise RuntimeError(f"{name} must be contiguous")
+    return t
+
+
+def prepare_pair(image1: torch.Tensor, image2: torch.Tensor, plan):
+    """Both images of a pair [B,3,H,W] (uint8 or float32, 0..255) -> (image1_pad, image2_pad) fp32 [B,3,plan.h_pad,plan.w_pad]: the
+    bicubic down-scale to plan.h_lr x plan.w_lr and the replicate padding of pad_for_multi_train (evaluation.py:67-89), or the
+    padding alone when the plan does not resize (scale 1, pad_for_multi_train_fixed) — one launch, as_prepare_pair.
+    `plan` = harness.query.query_plan(H, W, scale, divis_by)."""
+    _req_image(image1, "prepare_pair: image1"), _req_image(image2, "prepare_pair: image2")
+    if image1.dim() != 4 or image1.shape[1] != 3:
+        raise RuntimeError(f"prepare_pair: image1 must be [B,3,H,W], got {tuple(image1.shape)}")
+    if image1.shape != image2.shape or image1.dtype != image2.dtype or image1.device != image2.device:
+        raise RuntimeError(f"prepare_pair: image1 {tuple(image1.shape)} {image1.dtype} and image2 {tuple(image2.shape)} {image2.dtype} "
+                           "must share shape, dtype and device")
+    b, _, h, w = image1.shape
+    if b < 1 or h < 1 or w < 1:
+        raise RuntimeError(f"prepare_pair: empty input {tuple(image1.shape)}")
+    if (h, w) != (plan.h, plan.w):
+        raise RuntimeError(f"prepare_pair: the plan is for {plan.h}x{plan.w} images, got {h}x{w}")
+    out1 = torch.empty((b, 3, plan.h_pad, plan.w_pad), device=image1.device, dtype=torch.float32)
+    out2 = torch.empty_like(out1)
+    with _guard(image1.device):
+        L.check(L.load().as_prepare_pair(_p(image1), _p(image2), _p(out1), _p(out2), int(image1.dtype == torch.uint8), b, h, w,
+                                         plan.h_lr, plan.w_lr, plan.pad[0], plan.pad[1], plan.pad[2], plan.pad[3], _stream()),
+                "prepare_pair")
+    return out1, out2
+
+
+def query_grid(plan, batch: int, device) -> torch.Tensor:
+    """hr_coord fp32 [batch, plan.h_want * plan.w_want, 2] of pad_for_multi_train / pad_for_multi_train_fixed, written by the device
+    (as_query_grid): all `batch` copies, no host grid, no upload."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"query_grid: device must be a CUDA (HIP) device, got {device} — the anystereo hot path has no CPU fallback")
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    batch = int(batch)
+    if batch < 1:
+        raise RuntimeError(f"query_grid: batch must be positive, got {batch}")
+    h_crop, w_crop = plan.h_hr - plan.p[0] - plan.p[1], plan.w_hr - plan.p[2] - plan.p[3]  # as the C entry derives it
+    if h_crop < 1 or w_crop < 1:
+        raise RuntimeError(f"query_grid: the padding {tuple(plan.p)} leaves an empty crop of the {plan.h_hr}x{plan.w_hr} grid")
+    if 2 * batch * plan.h_want * plan.w_want > 2 ** 31 - 1:
+        raise RuntimeError(f"query_grid: {batch} x {plan.h_want} x {plan.w_want} x 2 elements exceed 2^31-1")
+    out = torch.empty((batch, plan.h_want * plan.w_want, 2), device=device, dtype=torch.float32)
+    with _guard(device):
+        L.check(L.load().as_query_grid(_p(out), batch, plan.h_hr, plan.w_hr, plan.p[0], plan.p[1], plan.p[2], plan.p[3], plan.h_want,
+                                       plan.w_want, _stream()), "query_grid")
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # convolutions (update block, MLP)
 # ------------------------------------------------------------------------------------------------
 

@@ -17,6 +17,9 @@ Stateless operators (reference call site):
     corr_sampler_forward / corr_sampler_backward                         sampler/sampler.cpp:24-45
     disparity_metrics(est, gt, valid?, noc?, gt_lo, gt_hi, thres) -> Tensor  evaluation.py:389-417, metrics.py:66-118 -> fp64 [N,B,19]
     lr_consistency(dl, dr, thr) -> Tensor                                experiment.py:286-296 -> uint8 [B,H,W]
+    prepare_pair(image1, image2, scale, divis_by, fixed) -> (Tensor, Tensor)  evaluation.py:67-89, evaluation_validate.py:92-106, utils.py:7-26
+    query_grid(image, scale, divis_by, fixed) -> Tensor                  the same lines -> hr_coord fp32 [B,Q,2] of the pair `image` [B,3,H,W]
+                                                                         belongs to (its shape and device are read, not its values)
 Operators that carry weights take them as tensors, in the reference module's parameter order:
     motion_encoder(disp, corr, weights[5], biases[5]) -> Tensor          update.py:84-92  (convc1, convc2, convd1, convd2, conv)
     convgru_step(h, cz, cr, cq, x[], weights[3], biases[3]) -> Tensor    update.py:33-41  (convz, convr, convq)
@@ -47,6 +50,8 @@ _lib.define("corr_sampler_forward(Tensor volume, Tensor coords, int radius) -> T
 _lib.define("corr_sampler_backward(Tensor volume, Tensor coords, Tensor corr_grad, int radius) -> Tensor")
 _lib.define("disparity_metrics(Tensor est, Tensor gt, Tensor? valid, Tensor? noc, float gt_lo, float gt_hi, float[] thres) -> Tensor")
 _lib.define("lr_consistency(Tensor dl, Tensor dr, float thr) -> Tensor")
+_lib.define("prepare_pair(Tensor image1, Tensor image2, float scale, int divis_by, bool fixed) -> (Tensor, Tensor)")
+_lib.define("query_grid(Tensor image, float scale, int divis_by, bool fixed) -> Tensor")
 _lib.define("motion_encoder(Tensor disp, Tensor corr, Tensor[] weights, Tensor[] biases) -> Tensor")
 _lib.define("convgru_step(Tensor h, Tensor cz, Tensor cr, Tensor cq, Tensor[] x, Tensor[] weights, Tensor[] biases) -> Tensor")
 _lib.define("disp_head(Tensor x, Tensor[] weights, Tensor[] biases) -> Tensor")
@@ -54,7 +59,7 @@ _lib.define("liif_upsample(Tensor[] feats, Tensor coord, Tensor[] weights, Tenso
 
 OPS = ("corr_build_pyramid", "geo_pyramid", "geo_corr_lookup", "gwc_volume", "disparity_regression", "structure_feature",
        "convex_upsample", "corr_sampler_forward", "corr_sampler_backward", "motion_encoder", "convgru_step", "disp_head",
-       "liif_upsample", "disparity_metrics", "lr_consistency")
+       "liif_upsample", "disparity_metrics", "lr_consistency", "prepare_pair", "query_grid")
 
 
 def _f(t: torch.Tensor) -> torch.Tensor:
@@ -127,6 +132,23 @@ def _disparity_metrics(est, gt, valid, noc, gt_lo, gt_hi, thres):
 
 def _lr_consistency(dl, dr, thr):
     return ops.lr_consistency(dl, dr, thr)
+
+
+def _plan(h, w, scale, divis_by, fixed):
+    from .harness.query import query_plan
+    return query_plan(h, w, scale, divis_by, fixed=fixed)
+
+
+def _prepare_pair(image1, image2, scale, divis_by, fixed):
+    if image1.dim() != 4:
+        raise RuntimeError(f"prepare_pair: image1 must be [B,3,H,W], got {tuple(image1.shape)}")
+    return ops.prepare_pair(image1, image2, _plan(image1.shape[-2], image1.shape[-1], scale, divis_by, fixed))
+
+
+def _query_grid(image, scale, divis_by, fixed):
+    if image.dim() != 4:
+        raise RuntimeError(f"query_grid: image must be [B,3,H,W], got {tuple(image.shape)}")
+    return ops.query_grid(_plan(image.shape[-2], image.shape[-1], scale, divis_by, fixed), image.shape[0], image.device)
 
 
 # ---- operators with weights: the models' own nn modules, called with the caller's tensors as parameters ----------
@@ -211,7 +233,8 @@ _IMPLS = {
     "convex_upsample": _convex_upsample, "corr_sampler_forward": _corr_sampler_forward,
     "corr_sampler_backward": _corr_sampler_backward, "motion_encoder": _motion_encoder, "convgru_step": _convgru_step,
     "disp_head": _disp_head, "liif_upsample": _liif_upsample,
-    "disparity_metrics": _disparity_metrics, "lr_consistency": _lr_consistency,
+    "disparity_metrics": _disparity_metrics, "lr_consistency": _lr_consistency, "prepare_pair": _prepare_pair,
+    "query_grid": _query_grid,
 }
 for _name, _fn in _IMPLS.items():
     _lib.impl(_name, _fn, "CUDA")

@@ -609,6 +609,32 @@ int as_disp_metrics(const float* est, const float* gt, const unsigned char* vali
                     void* stream);
 int as_lr_consistency(const float* dl, const float* dr, unsigned char* noc, int B, int H, int W, float thr, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation inputs and query grid on the device (csrc/prepare.hip)
+ *
+ * as_prepare_pair  replaces the two F.interpolate(mode='bicubic') and the two InputPadder.pad calls of pad_for_multi_train
+ *                  (evaluation.py:67-89), the pad calls of pad_for_multi_train_Fixed (evaluation_validate.py:92-106) and InputPadder
+ *                  itself (models/.../utils/utils.py:7-26) with one launch over both images.  image1 / image2 [B,3,H,W], fp32 or (is_uint8
+ *                  != 0) uint8; out1 / out2 fp32 [B,3,h_lr + pad_top + pad_bottom, w_lr + pad_left + pad_right], written in full.
+ *                  A padded pixel is the resized pixel at the index clamped into [0,h_lr) x [0,w_lr) (replicate padding after the
+ *                  resize).  The resize is upsample_bicubic2d(align_corners=False) without antialiasing (A = -0.75, source index not
+ *                  clamped at 0, taps clamped into the image, result not clamped to 0..255); h_lr == H and w_lr == W: no resize, the
+ *                  bits of F.pad(x.float(), mode='replicate').  uint8 input gives the bits of the same values as fp32.  h_lr > H or
+ *                  w_lr > W: AS_ERR_BAD_SHAPE (the protocol only down-scales).
+ * as_query_grid    replaces make_coord + the crop by the scaled padding + the bilinear F.interpolate of the coordinates + the upload
+ *                  and expand().contiguous() of hr_coord (evaluation.py:67-89; evaluation_validate.py:92-106 without the resize).
+ *                  hr_coord fp32 [B, h_want * w_want, 2] (written in full, all B copies): query (y, x) = (rows[y], cols[x]), where
+ *                  rows = make_coord(h_hr)[p_top : h_hr - p_bottom] and cols likewise, each resized 1-D as ATen's bilinear
+ *                  (align_corners=False) does when (h_hr - p_top - p_bottom, w_hr - p_left - p_right) != (h_want, w_want).  One
+ *                  rounding per operation (no FMA): seq[i] = fl(fl(-1 + 1/n) + fl(fl(2/n) * i)).  An empty crop: AS_ERR_BAD_SHAPE.
+ *                  hr_coord must be 8-byte aligned (a query is one 8-byte store), else AS_ERR_BAD_ARG; 16-byte alignment selects
+ *                  16-byte stores.
+ * Both: more than 2^31-1 elements in a tensor or B > 65535: AS_ERR_BAD_SHAPE. */
+int as_prepare_pair(const void* image1, const void* image2, float* out1, float* out2, int is_uint8, int B, int H, int W, int h_lr,
+                    int w_lr, int pad_top, int pad_bottom, int pad_left, int pad_right, void* stream);
+int as_query_grid(float* hr_coord, int B, int h_hr, int w_hr, int p_top, int p_bottom, int p_left, int p_right, int h_want, int w_want,
+                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif

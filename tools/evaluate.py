@@ -2,6 +2,8 @@
 has disparity k everywhere, so the right view's ground truth is k as well.  One JSON line on stdout (rank 0).
 
     python tools/evaluate.py --pairs 8 --height 256 --width 512 --scale 1.5 --iters 8 --protocol things
+    python tools/evaluate.py --pairs 4 --prep host                  # down-scale / pad / query grid with torch ops and a host-built grid
+    python tools/evaluate.py --pairs 4 --uint8                      # 8-bit images as a loader delivers them (--prep device only)
     python -m torch.distributed.run --nproc-per-node 2 tools/evaluate.py --pairs 8       # pairs sharded over the ranks
 
 The weights are the deterministic fill, so EPE here says nothing about a trained model: the
@@ -31,6 +33,9 @@ def main():
     ap.add_argument("--scale", type=float, default=1.5)
     ap.add_argument("--iters", type=int, default=8)
     ap.add_argument("--max-disp", type=float, default=None)
+    ap.add_argument("--prep", default="device", choices=["host", "device"],
+                    help="device: as_prepare_pair + as_query_grid (two launches); host: query.pad_for_multi_train + upload of the grid")
+    ap.add_argument("--uint8", action="store_true", help="feed the images as uint8 (rounded); needs --prep device")
     a = ap.parse_args()
 
     from anystereo import _lib
@@ -41,6 +46,8 @@ def main():
 
     if not torch.cuda.is_available():
         raise SystemExit("tools/evaluate.py needs a GPU: the models' hot path has no CPU fallback")
+    if a.uint8 and a.prep != "device":
+        raise SystemExit("--uint8 needs --prep device: the host path takes float images")
     rank, world, local = dist.env_rank()
     dev = torch.device("cuda", local % torch.cuda.device_count())
     torch.cuda.set_device(dev)
@@ -55,15 +62,18 @@ def main():
     def pairs():
         for i in dist.shard_indices(a.pairs, rank, world):
             i1, i2 = synthetic_pair(1, a.height, a.width, shift=a.shift, seed=1000 + i)
+            if a.uint8:
+                i1, i2 = i1.round().to(torch.uint8), i2.round().to(torch.uint8)
             gt = torch.full((1, a.height, a.width), float(a.shift), device=dev)
             valid = torch.ones((1, a.height, a.width), device=dev)
             extra = gt.clone() if a.protocol == "things" else torch.ones((1, a.height, a.width), dtype=torch.uint8, device=dev)
             yield i1.to(dev), i2.to(dev), gt, valid, extra
 
     divis_by = 32 if "IGEV" in a.model else 16
-    evaluate(model, list(pairs())[:1], scale=a.scale, iters=a.iters, protocol=a.protocol, divis_by=divis_by)  # warm-up, not counted
+    evaluate(model, list(pairs())[:1], scale=a.scale, iters=a.iters, protocol=a.protocol, divis_by=divis_by,
+             prep=a.prep)  # warm-up, not counted
     ev = Evaluator(a.protocol, max_disp=a.max_disp)
-    res = evaluate(model, pairs(), scale=a.scale, iters=a.iters, protocol=a.protocol, evaluator=ev, divis_by=divis_by)
+    res = evaluate(model, pairs(), scale=a.scale, iters=a.iters, protocol=a.protocol, evaluator=ev, divis_by=divis_by, prep=a.prep)
     local_rate, local_pairs = res["pairs_per_s"], res["pairs"]
     if world > 1:
         ev.merge()
@@ -76,7 +86,8 @@ def main():
     dist.finalize()
     if rank == 0:
         print(json.dumps({"tool": "evaluate", "model": a.model, "protocol": a.protocol, "n_gpus": world, "pairs": a.pairs,
-                          "size": [a.height, a.width], "scale": a.scale, "iters": a.iters, "gt_disparity": a.shift,
+                          "size": [a.height, a.width], "scale": a.scale, "prep": a.prep,
+                          "image_dtype": "uint8" if a.uint8 else "float32", "iters": a.iters, "gt_disparity": a.shift,
                           "weights": "deterministic fill", "pairs_per_s": round(sum(rates), 3),
                           "per_rank_pairs_per_s": [round(r, 3) for r in rates], "rank0_pairs": local_pairs,
                           "library": _lib.library_info(), **merged}))
