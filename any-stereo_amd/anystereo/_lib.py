@@ -160,6 +160,7 @@ SIGNATURES = {
     "as_lr_consistency": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     "as_prepare_pair": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
     "as_query_grid": (_i, [_vp] + [_i] * 9 + [_vp]),
+    "as_disp_images": (_i, [_vp] * 5 + [_i] * 3 + [C.c_float] * 3 + [_vp]),
 }
 
 _lib = None

@@ -246,7 +246,7 @@ class Evaluator:
 
 @torch.no_grad()
 def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", max_disp: Optional[float] = None, thres=(1, 2, 3),
-             divis_by: int = 32, evaluator: Optional[Evaluator] = None, prep: str = "host") -> dict:
+             divis_by: int = 32, evaluator: Optional[Evaluator] = None, prep: str = "host", images=None) -> dict:
     """Run `model` over `pairs` as the reference's validate_* loops do (evaluation.py:341-373): down-scale by `scale` and pad
     (`query.pad_for_multi_train`), query the full-resolution grid in test_mode, reshape [B,1,Q] -> [B,H,W] and feed an Evaluator.
 
@@ -256,6 +256,10 @@ def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", ma
     feed this one (a rank of a sharded dataset calls its `merge()` afterwards) instead of a new Evaluator(protocol, ...).
     prep: "host" = `query.pad_for_multi_train` (torch ops, the query grid built on the host and uploaded); "device" =
     `query.prepare_on_device` (two launches, nothing on the host; the images may be uint8).
+    images: an `images.ImageSink` (or None): every batch's prediction and gt go to its `add` — one more launch and non-blocking
+    copies, still no synchronisation inside the loop — and its `flush()` writes the PNG files after the one synchronisation (outside
+    the timed span); the result gains "images_written".  The sink's pinned host buffers are allocated inside the loop, once per
+    batch until its first flush (reused afterwards): that allocation is in the timed span.  With None nothing changes.
 
     Only the last GRU iteration is evaluated: in test_mode the models up-sample the final disparity alone
     (continuous_IGEVstereo.py:267-268), so a per-iteration curve would cost one up-sampling pass per iteration."""
@@ -282,8 +286,12 @@ def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", ma
             ev.update(est, gt, valid, gt_right=extra)
         else:
             ev.update(est, gt, valid, noc=extra)
+        if images is not None:
+            images.add(est[0], gt)
         n_pairs += bs
     res = ev.result()  # the one synchronisation
     dt = time.perf_counter() - t0
     res.update(pairs=n_pairs, seconds=dt, pairs_per_s=(n_pairs / dt if dt > 0 else 0.0))
+    if images is not None:
+        res["images_written"] = len(images.flush())
     return res

@@ -469,6 +469,70 @@ def lr_consistency(dl: torch.Tensor, dr: torch.Tensor, thr: float = 3.0) -> torc
     return noc
 
 
+def disparity_images(disp: torch.Tensor, gt: Optional[torch.Tensor] = None, max_disp: float = 192.0, color: bool = True,
+                     error: Optional[bool] = None, enc16: bool = False, abs_thres: float = 3.0, rel_thres: float = 0.05):
+    """The evaluation pictures of a prediction in one pass (csrc/eval_images.hip): -> (color | None, error | None, enc16 | None).
+    disp fp32 [B,H,W] (or [B,1,H,W]), gt likewise or None.
+    color uint8 [B,H,W,3]: Disp_to_color(disp, max_disp) (evaluation.py:35-65) quantised as save_image does;
+    error uint8 [B,H,W,3]: the KITTI error map of disp against gt (visualization.py:30-55); `error=None` means "when gt is given";
+    enc16 uint8 [B,H,W,2]: clamp(rint(disp * 256), 0, 65535), high byte first (a 16-bit PNG's samples).
+    The bytes equal the quantised reference; a NaN disparity is black in color and 0 in enc16.  No synchronisation."""
+    _req(disp, "disp")
+    if disp.dim() == 4 and disp.shape[1] == 1:
+        disp = disp[:, 0]
+    if disp.dim() != 3:
+        raise RuntimeError(f"disparity_images: disp must be [B,H,W] or [B,1,H,W], got {tuple(disp.shape)}")
+    if gt is not None:
+        _req(gt, "gt")
+        if gt.dim() == 4 and gt.shape[1] == 1:
+            gt = gt[:, 0]
+        if tuple(gt.shape) != tuple(disp.shape) or gt.device != disp.device:
+            raise RuntimeError(f"disparity_images: disp {tuple(disp.shape)} on {disp.device} does not match gt {tuple(gt.shape)} on {gt.device}")
+    if error is None:
+        error = gt is not None
+    if error and gt is None:
+        raise RuntimeError("disparity_images: the error picture needs gt")
+    if not (color or error or enc16):
+        raise RuntimeError("disparity_images: no output requested")
+    b, h, w = disp.shape
+    if b < 1 or h < 1 or w < 1:
+        raise RuntimeError(f"disparity_images: empty input {tuple(disp.shape)}")
+    for name, v in (("max_disp", max_disp), ("abs_thres", abs_thres), ("rel_thres", rel_thres)):
+        if not (0.0 < float(v) < float("inf")):
+            raise RuntimeError(f"disparity_images: {name} must be finite and positive, got {v}")
+    if 3 * b * h * w > 2 ** 31 - 1:
+        raise RuntimeError(f"disparity_images: {b} x {h} x {w} x 3 bytes exceed 2^31-1")
+    c = torch.empty((b, h, w, 3), device=disp.device, dtype=torch.uint8) if color else None
+    e = torch.empty((b, h, w, 3), device=disp.device, dtype=torch.uint8) if error else None
+    n = torch.empty((b, h, w, 2), device=disp.device, dtype=torch.uint8) if enc16 else None
+    disparity_images_out(disp, gt, c, e, n, max_disp, abs_thres, rel_thres)
+    return c, e, n
+
+
+def disparity_images_out(disp: torch.Tensor, gt: Optional[torch.Tensor], color: Optional[torch.Tensor], error: Optional[torch.Tensor],
+                         enc16: Optional[torch.Tensor], max_disp: float = 192.0, abs_thres: float = 3.0, rel_thres: float = 0.05) -> None:
+    """`disparity_images` into the caller's buffers: disp / gt fp32 [B,H,W] contiguous, color / error uint8 [B,H,W,3] and enc16 uint8
+    [B,H,W,2] contiguous or None (at least one given); every byte of a given buffer is written.  A buffer that does not start on a
+    4-byte boundary is refused (the kernel stores whole dwords)."""
+    _req(disp, "disp")
+    if disp.dim() != 3:
+        raise RuntimeError(f"disparity_images: disp must be [B,H,W], got {tuple(disp.shape)}")
+    b, h, w = disp.shape
+    if gt is not None:
+        _req(gt, "gt")
+        if tuple(gt.shape) != (b, h, w) or gt.device != disp.device:
+            raise RuntimeError(f"disparity_images: disp {tuple(disp.shape)} on {disp.device} does not match gt {tuple(gt.shape)} on {gt.device}")
+    for name, t, ch in (("color", color, 3), ("error", error, 3), ("enc16", enc16, 2)):
+        if t is None:
+            continue
+        _req(t, name, torch.uint8)
+        if tuple(t.shape) != (b, h, w, ch) or t.device != disp.device:
+            raise RuntimeError(f"disparity_images: {name} must be {(b, h, w, ch)} on {disp.device}, got {tuple(t.shape)} on {t.device}")
+    with _guard(disp.device):
+        L.check(L.load().as_disp_images(_p(disp), _p(gt), _p(color), _p(error), _p(enc16), b, h, w, float(max_disp), float(abs_thres),
+                                        float(rel_thres), _stream()), "disp_images")
+
+
 # ------------------------------------------------------------------------------------------------
 # evaluation inputs: bicubic down-scale + replicate pad of the pair, and the query grid (csrc/prepare.hip)
 # ------------------------------------------------------------------------------------------------

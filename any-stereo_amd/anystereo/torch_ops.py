@@ -20,6 +20,9 @@ Stateless operators (reference call site):
     prepare_pair(image1, image2, scale, divis_by, fixed) -> (Tensor, Tensor)  evaluation.py:67-89, evaluation_validate.py:92-106, utils.py:7-26
     query_grid(image, scale, divis_by, fixed) -> Tensor                  the same lines -> hr_coord fp32 [B,Q,2] of the pair `image` [B,3,H,W]
                                                                          belongs to (its shape and device are read, not its values)
+    disparity_images(disp, gt?, max_disp, color, error?, enc16, abs_thres, rel_thres) -> (Tensor?, Tensor?, Tensor?)
+                                                                         evaluation.py:35-65 + save_image, visualization.py:30-55 ->
+                                                                         uint8 color [B,H,W,3], error [B,H,W,3], enc16 [B,H,W,2]
 Operators that carry weights take them as tensors, in the reference module's parameter order:
     motion_encoder(disp, corr, weights[5], biases[5]) -> Tensor          update.py:84-92  (convc1, convc2, convd1, convd2, conv)
     convgru_step(h, cz, cr, cq, x[], weights[3], biases[3]) -> Tensor    update.py:33-41  (convz, convr, convq)
@@ -52,6 +55,8 @@ _lib.define("disparity_metrics(Tensor est, Tensor gt, Tensor? valid, Tensor? noc
 _lib.define("lr_consistency(Tensor dl, Tensor dr, float thr) -> Tensor")
 _lib.define("prepare_pair(Tensor image1, Tensor image2, float scale, int divis_by, bool fixed) -> (Tensor, Tensor)")
 _lib.define("query_grid(Tensor image, float scale, int divis_by, bool fixed) -> Tensor")
+_lib.define("disparity_images(Tensor disp, Tensor? gt, float max_disp, bool color, bool? error, bool enc16, float abs_thres, "
+            "float rel_thres) -> (Tensor?, Tensor?, Tensor?)")
 _lib.define("motion_encoder(Tensor disp, Tensor corr, Tensor[] weights, Tensor[] biases) -> Tensor")
 _lib.define("convgru_step(Tensor h, Tensor cz, Tensor cr, Tensor cq, Tensor[] x, Tensor[] weights, Tensor[] biases) -> Tensor")
 _lib.define("disp_head(Tensor x, Tensor[] weights, Tensor[] biases) -> Tensor")
@@ -59,7 +64,7 @@ _lib.define("liif_upsample(Tensor[] feats, Tensor coord, Tensor[] weights, Tenso
 
 OPS = ("corr_build_pyramid", "geo_pyramid", "geo_corr_lookup", "gwc_volume", "disparity_regression", "structure_feature",
        "convex_upsample", "corr_sampler_forward", "corr_sampler_backward", "motion_encoder", "convgru_step", "disp_head",
-       "liif_upsample", "disparity_metrics", "lr_consistency", "prepare_pair", "query_grid")
+       "liif_upsample", "disparity_metrics", "lr_consistency", "prepare_pair", "query_grid", "disparity_images")
 
 
 def _f(t: torch.Tensor) -> torch.Tensor:
@@ -151,6 +156,10 @@ def _query_grid(image, scale, divis_by, fixed):
     return ops.query_grid(_plan(image.shape[-2], image.shape[-1], scale, divis_by, fixed), image.shape[0], image.device)
 
 
+def _disparity_images(disp, gt, max_disp, color, error, enc16, abs_thres, rel_thres):
+    return ops.disparity_images(disp, gt, max_disp, color, error, enc16, abs_thres, rel_thres)
+
+
 # ---- operators with weights: the models' own nn modules, called with the caller's tensors as parameters ----------
 _modules: dict = {}
 
@@ -234,7 +243,7 @@ _IMPLS = {
     "corr_sampler_backward": _corr_sampler_backward, "motion_encoder": _motion_encoder, "convgru_step": _convgru_step,
     "disp_head": _disp_head, "liif_upsample": _liif_upsample,
     "disparity_metrics": _disparity_metrics, "lr_consistency": _lr_consistency, "prepare_pair": _prepare_pair,
-    "query_grid": _query_grid,
+    "query_grid": _query_grid, "disparity_images": _disparity_images,
 }
 for _name, _fn in _IMPLS.items():
     _lib.impl(_name, _fn, "CUDA")

@@ -635,6 +635,32 @@ int as_prepare_pair(const void* image1, const void* image2, float* out1, float* 
 int as_query_grid(float* hr_coord, int B, int h_hr, int w_hr, int p_top, int p_bottom, int p_left, int p_right, int h_want, int w_want,
                   void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Evaluation pictures on the device (csrc/eval_images.hip)
+ *
+ * as_disp_images   replaces, per image of every validate_* loop, the `.cpu()` of the full-resolution prediction followed by
+ *                  Disp_to_color (evaluation.py:35-65, written with save_image at :196,318,434,543) and by
+ *                  disp_error_image_func.forward (metrics_utils/visualization.py:30-55, called at evaluation.py:187,309,425,533) with
+ *                  one pass that reads disp and gt once and writes 8-bit pixels.  disp, gt fp32 [B,H,W];
+ *                    color uint8 [B,H,W,3]  Disp_to_color(disp, max_disp) quantised as torchvision's save_image does,
+ *                                           q = (uint8) clamp(fl(fl(v * 255) + 0.5), 0, 255), interleaved RGB;
+ *                    error uint8 [B,H,W,3]  the KITTI error map of est = disp against gt (abs_thres 3, rel_thres 0.05 in the
+ *                                           reference): ten colour bands, black where gt <= 0, the legend in the top-left
+ *                                           10 x 200 pixels (clipped by the image, overriding the mask); no dilation (a TODO in
+ *                                           the reference);
+ *                    enc16 uint8 [B,H,W,2]  n = clamp(rint(disp * 256), 0, 65535), ties to even, HIGH byte first: a 16-bit
+ *                                           grey PNG's samples, the inverse of readDispKITTI (frame_utils.py:124-127).
+ *                  Any subset of the three outputs may be NULL; each requested output is written in full.  Every step the
+ *                  reference rounds is one fp32 rounding (IEEE division, no FMA), so color / error equal the quantised reference
+ *                  byte for byte.  NaN and inf: a disp of -inf (or < 0) is black and of +inf (or >= max_disp) white in color; a
+ *                  NaN disp is (0,0,0) there (the reference hands save_image a NaN, whose cast is undefined) and 0 in enc16; NaN
+ *                  or +-inf estimates fall in no error band and are black, like gt <= 0.
+ *                  AS_ERR_BAD_ARG: NULL disp, all three outputs NULL, error without gt, a non-positive B, H or W, max_disp,
+ *                  abs_thres or rel_thres not finite and positive, an output that is not 4-byte aligned (the kernel stores whole
+ *                  dwords; disp / gt 16-byte aligned selects 16-byte loads).  AS_ERR_BAD_SHAPE: 3 * B * H * W > 2^31-1. */
+int as_disp_images(const float* disp, const float* gt, unsigned char* color, unsigned char* error, unsigned char* enc16, int B, int H,
+                   int W, float max_disp, float abs_thres, float rel_thres, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@ has disparity k everywhere, so the right view's ground truth is k as well.  One 
     python tools/evaluate.py --pairs 4 --prep host                  # down-scale / pad / query grid with torch ops and a host-built grid
     python tools/evaluate.py --pairs 4 --uint8                      # 8-bit images as a loader delivers them (--prep device only)
     python -m torch.distributed.run --nproc-per-node 2 tools/evaluate.py --pairs 8       # pairs sharded over the ranks
+    python tools/evaluate.py --pairs 2 --save-images out/           # disp_{i}.png (colour map) and error_{i}.png per pair; --enc16 adds
+                                                                    # the 16-bit disp16_{i}.png, --image-limit N stops after N pairs
 
 The weights are the deterministic fill, so EPE here says nothing about a trained model: the
 line shows that the protocol runs on the device, what it counts and how fast.  No dataset readers.
@@ -36,11 +38,17 @@ def main():
     ap.add_argument("--prep", default="device", choices=["host", "device"],
                     help="device: as_prepare_pair + as_query_grid (two launches); host: query.pad_for_multi_train + upload of the grid")
     ap.add_argument("--uint8", action="store_true", help="feed the images as uint8 (rounded); needs --prep device")
+    ap.add_argument("--save-images", default=None, metavar="DIR",
+                    help="write the colourised disparity and the error map of every pair as PNG files (harness/images.py); with several "
+                         "ranks each writes into DIR/rank<r>")
+    ap.add_argument("--image-limit", type=int, default=None, help="stop writing pictures after this many pairs (per rank)")
+    ap.add_argument("--enc16", action="store_true", help="with --save-images: also the 16-bit disparity PNG (disparity * 256)")
     a = ap.parse_args()
 
     from anystereo import _lib
     from anystereo.harness import dist
     from anystereo.harness.evaluate import Evaluator, evaluate
+    from anystereo.harness.images import ImageSink
     from anystereo.harness.synthetic import fill_module_deterministic, synthetic_pair
     from anystereo.models import __models__, default_args
 
@@ -73,14 +81,21 @@ def main():
     evaluate(model, list(pairs())[:1], scale=a.scale, iters=a.iters, protocol=a.protocol, divis_by=divis_by,
              prep=a.prep)  # warm-up, not counted
     ev = Evaluator(a.protocol, max_disp=a.max_disp)
-    res = evaluate(model, pairs(), scale=a.scale, iters=a.iters, protocol=a.protocol, evaluator=ev, divis_by=divis_by, prep=a.prep)
+    sink = None
+    if a.save_images:
+        sink = ImageSink(a.save_images if world == 1 else os.path.join(a.save_images, f"rank{rank}"), enc16=a.enc16, limit=a.image_limit)
+    res = evaluate(model, pairs(), scale=a.scale, iters=a.iters, protocol=a.protocol, evaluator=ev, divis_by=divis_by, prep=a.prep,
+                   images=sink)
     local_rate, local_pairs = res["pairs_per_s"], res["pairs"]
+    written = [0.0] * world
+    written[rank] = float(res.get("images_written", 0))
     if world > 1:
         ev.merge()
         merged = ev.result()
         rates = [0.0] * world
         rates[rank] = local_rate
         rates = dist.sum_over_ranks(rates)
+        written = dist.sum_over_ranks(written)
     else:
         merged, rates = {k: res[k] for k in ("all", "noc", "occ", "images")}, [local_rate]
     dist.finalize()
@@ -90,7 +105,8 @@ def main():
                           "image_dtype": "uint8" if a.uint8 else "float32", "iters": a.iters, "gt_disparity": a.shift,
                           "weights": "deterministic fill", "pairs_per_s": round(sum(rates), 3),
                           "per_rank_pairs_per_s": [round(r, 3) for r in rates], "rank0_pairs": local_pairs,
-                          "library": _lib.library_info(), **merged}))
+                          "library": _lib.library_info(), **({"images_written": int(sum(written))} if sink is not None else {}),
+                          **merged}))
 
 
 if __name__ == "__main__":
