@@ -598,6 +598,105 @@ def query_grid(plan, batch: int, device) -> torch.Tensor:
 
 
 # ------------------------------------------------------------------------------------------------
+# multi-scale training batches: queries, gathered ground truth and the 1/4-resolution target (csrc/train_batch.hip)
+# ------------------------------------------------------------------------------------------------
+
+# AS_TQ_* of include/anystereo_hip.h; the one Python copy of the table (harness.batches takes it from here)
+TRAIN_QUERY_MODES = {"dense": 0, "dense_all": 1, "sparse": 2, "sparse_ordered": 3}
+_train_ws = {}  # (device index, stream handle) -> uint8 scratch of the sparse modes; grows, never shrinks.  One buffer per stream:
+# calls on one stream use it in stream order, calls on different streams of a device never share a pixel list.
+
+
+def host_scales(scales, n: int, what: str) -> List[float]:
+    """`scales` (a sequence of n numbers or a host tensor of n values) as the fp32 values the kernels receive, held in Python
+    floats.  Shared with harness.batches, so that the device path and its host restatement round the scales in one place."""
+    if isinstance(scales, torch.Tensor):
+        if scales.is_cuda:
+            raise RuntimeError(f"{what}: scales must be host numbers (reading them from the device would synchronise; the crop sizes "
+                               "follow from them on the host anyway: h_hr = round(h_lr * scale))")
+        scales = scales.reshape(-1).tolist()
+    if len(scales) != n:
+        raise RuntimeError(f"{what}: {len(scales)} scales for {n} crops")
+    return [C.c_float(float(v)).value for v in scales]
+
+
+def _host_scales(scales, n: int, what: str):
+    return (C.c_float * n)(*host_scales(scales, n, what))
+
+
+def _req_crops(disps, what: str):
+    """A ragged batch of crops -> (device, pointer table, h[], w[]) for the C entries."""
+    if not isinstance(disps, (list, tuple)) or len(disps) == 0:
+        raise RuntimeError(f"{what}: disps must be a non-empty list of float32 [h, w] tensors")
+    for b, d in enumerate(disps):
+        _req(d, f"{what}: disps[{b}]")
+        if d.dim() != 2 or d.numel() == 0:
+            raise RuntimeError(f"{what}: disps[{b}] must be a non-empty [h, w] tensor, got {tuple(d.shape)}")
+        if d.device != disps[0].device:
+            raise RuntimeError(f"{what}: disps[{b}] is on {d.device}, disps[0] on {disps[0].device}")
+    n = len(disps)
+    ptrs, keep = L.ptr_array([d.data_ptr() for d in disps])
+    hs = (C.c_int * n)(*[d.shape[0] for d in disps])
+    ws = (C.c_int * n)(*[d.shape[1] for d in disps])
+    return disps[0].device, ptrs, keep, hs, ws
+
+
+def train_queries(disps, q: int, mode: str, seed: int, scales=None):
+    """The queries of a multi-scale training batch and the ground truth at them (stereo_datasets.py:166-211), made on the device:
+    `disps` = B float32 crops [h_b, w_b] of different sizes -> (hr_coord fp32 [B,Q,2], hr_disp fp32 [B,1,Q], index int32 [B,Q],
+    n_valid int32 [B]); `mode` one of TRAIN_QUERY_MODES, the random draws a function of (seed, b, mode) (as_train_queries).
+    `scales` (B host numbers): a fifth output, scale fp32 [B,1], written by the same launch — the batch's `scale` tensor without a
+    host-to-device copy (one from pageable memory would wait for everything queued on the stream).  No synchronisation: n_valid
+    stays on the device (harness.batches.validate reads it).  The sparse modes' scratch is cached per (device, stream)."""
+    if mode not in TRAIN_QUERY_MODES:
+        raise RuntimeError(f"train_queries: unknown mode {mode!r}: one of {sorted(TRAIN_QUERY_MODES)}")
+    dev, ptrs, keep, hs, ws = _req_crops(disps, "train_queries")
+    b, q, m = len(disps), int(q), TRAIN_QUERY_MODES[mode]
+    lib = L.load()
+    need = int(lib.as_train_queries_ws_bytes(hs, ws, b, m))
+    if need < 0:
+        L.check(need, "train_queries_ws_bytes")
+    if q < 1 or 2 * b * q > 2 ** 31 - 1:
+        raise RuntimeError(f"train_queries: Q={q} with B={b}: need 1 <= Q and 2 * B * Q <= 2^31-1")
+    sc = None if scales is None else _host_scales(scales, b, "train_queries")
+    with _guard(dev):
+        stream = _stream()
+        scratch = None
+        if need:
+            key = (dev.index, stream.value)
+            scratch = _train_ws.get(key)
+            if scratch is None or scratch.numel() < need:
+                scratch = _train_ws[key] = torch.empty(need, device=dev, dtype=torch.uint8)
+        hr_coord = torch.empty((b, q, 2), device=dev, dtype=torch.float32)
+        hr_disp = torch.empty((b, 1, q), device=dev, dtype=torch.float32)
+        index = torch.empty((b, q), device=dev, dtype=torch.int32)
+        n_valid = torch.empty((b,), device=dev, dtype=torch.int32)
+        scale = None if sc is None else torch.empty((b, 1), device=dev, dtype=torch.float32)
+        L.check(lib.as_train_queries(ptrs, hs, ws, b, q, m, int(seed) & 0xFFFFFFFFFFFFFFFF, _p(hr_coord), _p(hr_disp), _p(index),
+                                     _p(n_valid), sc, _p(scale), _p(scratch), 0 if scratch is None else scratch.numel(), stream),
+                "train_queries")
+    del keep
+    return (hr_coord, hr_disp, index, n_valid) if scale is None else (hr_coord, hr_disp, index, n_valid, scale)
+
+
+def low_disp(disps, scales, out_hw):
+    """low_disp_gt fp32 [B, h_out, w_out] of --supervise_init (stereo_datasets.py:151-156): every crop of `disps` (B float32 [h_b, w_b]
+    tensors) resized bilinearly to out_hw = (h_lr // 4, w_lr // 4) and divided by 4 * scale_b (`scales`: B host numbers) — one
+    launch per 8 samples (as_low_disp)."""
+    dev, ptrs, keep, hs, ws = _req_crops(disps, "low_disp")
+    b = len(disps)
+    sc = _host_scales(scales, b, "low_disp")
+    h_out, w_out = int(out_hw[0]), int(out_hw[1])
+    if h_out < 1 or w_out < 1:
+        raise RuntimeError(f"low_disp: empty output {h_out}x{w_out}")
+    out = torch.empty((b, h_out, w_out), device=dev, dtype=torch.float32)
+    with _guard(dev):
+        L.check(L.load().as_low_disp(ptrs, hs, ws, sc, _p(out), b, h_out, w_out, _stream()), "low_disp")
+    del keep
+    return out
+
+
+# ------------------------------------------------------------------------------------------------
 # convolutions (update block, MLP)
 # ------------------------------------------------------------------------------------------------
 

@@ -661,6 +661,61 @@ int as_query_grid(float* hr_coord, int B, int h_hr, int w_hr, int p_top, int p_b
 int as_disp_images(const float* disp, const float* gt, unsigned char* color, unsigned char* error, unsigned char* enc16, int B, int H,
                    int W, float max_disp, float abs_thres, float rel_thres, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Multi-scale training batches on the device (csrc/train_batch.hip)
+ *
+ * What of a training sample is a function of (ground-truth crop, scale, seed): the tail of StereoDataset.__getitem__
+ * (models/.../stereo_datasets.py:148-212).  A batch is RAGGED: `crops` is a HOST array of B device pointers, crop b is fp32
+ * [h_hr[b], w_hr[b]] (h_hr / w_hr host arrays), N_b = h_hr[b] * w_hr[b], pixel i = y * w_hr + x.  Nothing is padded.
+ *
+ * as_train_queries  replaces to_pixel_samples / make_coord of the whole crop (stereo_datasets.py:18-41,167), the draws
+ *                  np.random.choice(n, k, replace=False) and the gathers of :189-193 (AS_TQ_DENSE), the pass-through of :166-168,194
+ *                  (AS_TQ_DENSE_ALL), the boolean-mask splits, draws and concatenations of :170-188 (AS_TQ_SPARSE) and of :195-211
+ *                  (AS_TQ_SPARSE_ORDERED), and the upload of the result.  Per sample b, Q queries:
+ *                    DENSE           query j = pixel pi(j), pi a keyed bijection of [0, N)
+ *                    DENSE_ALL       query j = pixel j (Q == N for every sample)
+ *                    SPARSE          valid = crop > 0 (NaN is invalid, +inf valid), V = #valid.  Q < V: query j = the pi(j)-th valid
+ *                                    pixel, pi over [0, V).  Otherwise the V valid pixels in raster order, then query V + j = the
+ *                                    pi(j)-th invalid pixel, pi over [0, N - V)
+ *                    SPARSE_ORDERED  the valid pixels in raster order, then the invalid ones in raster order, cut at Q; with V > Q
+ *                                    (the reference asserts) the first Q valid pixels — the caller sees V in n_valid
+ *                  pi(j): a Feistel network of 6 rounds over the next power-of-two domain of n (halves of floor(bits/2) and
+ *                  ceil(bits/2) bits that swap every round, round function = a 32-bit multiply-xorshift mix of the right half and the
+ *                  round key), walked until the value falls below n (cycle walking).  The round keys are a function of
+ *                  (seed, b, mode, round) alone, so a query depends on no other query: no sort, no rejection table.
+ *                  Outputs, all written in full: hr_coord fp32 [B,Q,2] = (row value, column value) of make_coord([h_hr, w_hr]) at the
+ *                  pixel, one rounding per operation (no FMA): fl(fl(-1 + 1/n) + fl(fl(2/n) * i)); hr_disp fp32 [B,1,Q] = the
+ *                  crop's value, a bit copy (inf and NaN included); index int32 [B,Q] = the flat pixel of each query; n_valid int32
+ *                  [B] = V in the sparse modes, N in the dense ones.
+ *                  scale (B host floats, the arry_scale of :168) and scale_out (device fp32 [B]) may be NULL: with both, the
+ *                  kernel also writes scale_out[b] = scale[b], so the batch's scale tensor needs no host-to-device copy (a copy
+ *                  from pageable memory waits for the stream).
+ *                  ws: device scratch of as_train_queries_ws_bytes(h_hr, w_hr, B, mode) bytes = 4 * sum_b (N_b + ceil(N_b / 2048))
+ *                  in the sparse modes (the ordered pixel list of every sample and its per-tile offsets, built by a count, a
+ *                  scan and a scatter launch; no block waits for another), 0 in the dense modes (ws may be NULL).
+ *                  A launch carries the table of 8 samples; larger batches are chunked inside.
+ *                  AS_ERR_BAD_ARG: a NULL pointer (a crop pointer included), B, Q or a size <= 0, an unknown mode, hr_coord not
+ *                  8-byte aligned, ws not 4-byte aligned or smaller than needed, scale_out without scale, a scale that is not
+ *                  finite and positive.  AS_ERR_BAD_SHAPE: N_b < Q (every mode but
+ *                  DENSE_ALL), N_b != Q (DENSE_ALL), N_b or 2 * B * Q above 2^31-1.
+ * as_low_disp      replaces cv2.resize(flow, [w_lr//4, h_lr//4], INTER_LINEAR) / (4 * scale) (stereo_datasets.py:151-152,156): out
+ *                  fp32 [B,h_out,w_out], written in full, = the bilinear resize of crop b followed by ONE IEEE division by
+ *                  (float)(4 * scale[b]) (scale: host floats).  The resize is ATen's upsample_bilinear2d(align_corners=False)
+ *                  without antialiasing: ratio = (float)in / (float)out, src = max(ratio * (dst + 0.5f) - 0.5f, 0), i0 = (int)src,
+ *                  i1 = min(i0 + 1, in - 1), l1 = src - i0, l0 = 1 - l1, value = ly0 * (lx0 * v00 + lx1 * v01) + ly1 * (lx0 * v10 +
+ *                  lx1 * v11), no FMA.  AS_ERR_BAD_ARG: a NULL pointer, a size <= 0, a scale that is not finite and positive.
+ *                  AS_ERR_BAD_SHAPE: N_b or B * h_out * w_out above 2^31-1, h_out above 65535 * 4. */
+#define AS_TQ_DENSE 0
+#define AS_TQ_DENSE_ALL 1
+#define AS_TQ_SPARSE 2
+#define AS_TQ_SPARSE_ORDERED 3
+int64_t as_train_queries_ws_bytes(const int* h_hr, const int* w_hr, int B, int mode);
+int as_train_queries(const float* const* crops, const int* h_hr, const int* w_hr, int B, int Q, int mode, uint64_t seed,
+                     float* hr_coord, float* hr_disp, int* index, int* n_valid, const float* scale, float* scale_out, void* ws,
+                     int64_t ws_bytes, void* stream);
+int as_low_disp(const float* const* crops, const int* h_hr, const int* w_hr, const float* scale, float* out, int B, int h_out,
+                int w_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
