@@ -45,6 +45,19 @@ class ConvDesc(C.Structure):
     ]
 
 
+class ConvKnobs(C.Structure):
+    """as_conv_knobs (include/anystereo_hip.h): the AS_CONV_* dispatch knobs."""
+    _fields_ = [(n, C.c_int) for n in ("lean", "xcd", "xcd_stagger", "lean_offset", "ksplit_max", "dma", "wide", "wide64",
+                                       "small_dma", "prefer64")]
+
+
+class ConvPlan(C.Structure):
+    """as_conv_plan (include/anystereo_hip.h): what as_conv2d launches for a descriptor."""
+    _fields_ = [(n, C.c_int) for n in ("family", "KS", "TW", "BN", "NSUB", "S", "FAST", "LEAN", "epilogue", "finish", "finish_epilogue",
+                                       "ksplit", "tiles_x", "tiles_y", "n_tiles", "chunks", "H", "W", "Hi", "Wi", "all_bs", "xcd_map",
+                                       "stagger", "lean_offset", "dual", "block", "lds")] + [("grid", C.c_int64), ("finish_grid", C.c_int64)]
+
+
 # name -> (restype, argtypes); every symbol include/anystereo_hip.h declares
 SIGNATURES = {
     "as_set_precision": (_i, [_i]),
@@ -78,6 +91,7 @@ SIGNATURES = {
     "as_gwc_volume_fwd": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
     "as_disparity_regression": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "as_conv2d": (_i, [C.POINTER(ConvDesc), _vp]),
+    "as_conv2d_plan": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvKnobs), C.POINTER(ConvPlan)]),
     "as_conv_ws_elems": (C.c_int64, [_i, _i, _i, _i]),
     "as_conv_pack_size": (C.c_int64, [_i, _i, _i]),
     "as_conv_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _vp]),

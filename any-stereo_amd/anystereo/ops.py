@@ -856,6 +856,44 @@ class BS8:
         return v.permute(0, 1, 4, 2, 3).reshape(b, c8 * 8, h, w)[:, :self.c].contiguous()
 
 
+def conv_plan(desc_or_args, knobs: Optional[dict] = None) -> dict:
+    """What as_conv2d would launch (as_conv2d_plan): the kernel's template tuple, grid, block, LDS, K split, tiling, dual mode.
+    desc_or_args: an L.ConvDesc, or the dict of a single-source convolution as conv2d would describe it: B, H, W, Cin, Cout and
+    optionally KS (3), precision (1), epilogue, stride, act, blocked (the source is a BS8), dual (a second convolution of the same
+    shape rides along), ws (True: split-K scratch as conv2d gives it).
+    Only the L.ConvDesc form reports a real call exactly: the dict form describes no blocked result, output window, add or second
+    source shape of its own (a blocked result changes `finish_grid`), and takes the workspace whenever precision is 1 at stride 1.
+    knobs: AS_CONV_* values by field name (lean, xcd, ...) over the defaults; None = the process's own.
+    Host arithmetic only: no GPU, no tensor."""
+    lib = L.load()
+    d = desc_or_args
+    if not isinstance(d, L.ConvDesc):
+        a, d, fake = dict(desc_or_args), L.ConvDesc(), 1 << 20  # the planner never dereferences a data pointer
+        d.B, d.H, d.W, d.Cin, d.Cout, d.KS = a["B"], a["H"], a["W"], a["Cin"], a["Cout"], a.get("KS", 3)
+        d.precision, d.epilogue, d.stride, d.act = a.get("precision", 1), a.get("epilogue", L.EPI_LINEAR), a.get("stride", 1), a.get("act", 0)
+        d.src[0], d.src_c[0], d.n_src, d.src_bs[0] = fake, d.Cin, 1, 1 if a.get("blocked") else 0
+        d.wpack = d.out = fake
+        if d.epilogue == L.EPI_RELU_TAPS:
+            d.tap_w = fake
+        elif d.epilogue != L.EPI_LINEAR:
+            d.out2 = d.h = d.z = fake
+        if a.get("dual"):
+            d.dual, d.src2, d.wpack2, d.src2_bs = 1, fake, fake, d.src_bs[0]
+        if a.get("ws", True) and d.precision == 1 and d.stride == 1:
+            d.ws_elems = lib.as_conv_ws_elems(d.B, d.Cout, d.H, d.W)
+            d.ws = fake if d.ws_elems > 0 else 0
+    k = None
+    if knobs is not None:
+        k = L.ConvKnobs(lean=1, xcd=2, xcd_stagger=0, lean_offset=0, ksplit_max=8, dma=1, wide=1, wide64=1, small_dma=1, prefer64=0)
+        for name, v in knobs.items():
+            if not hasattr(k, name):
+                raise RuntimeError(f"conv_plan: unknown knob {name}")
+            setattr(k, name, int(v))
+    plan = L.ConvPlan()
+    L.check(lib.as_conv2d_plan(C.byref(d), None if k is None else C.byref(k), C.byref(plan)), "conv2d_plan")
+    return {n: int(getattr(plan, n)) for n, _ in L.ConvPlan._fields_}
+
+
 def conv2d(srcs: Sequence[torch.Tensor], pack: PackedConv, act: int = L.ACT_NONE, add: Optional[torch.Tensor] = None,
            add_coff: int = 0, out: Optional[torch.Tensor] = None, out_coff: int = 0, epilogue: int = L.EPI_LINEAR,
            h: Optional[torch.Tensor] = None, z: Optional[torch.Tensor] = None, out2: Optional[torch.Tensor] = None,

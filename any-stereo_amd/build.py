@@ -53,7 +53,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
     stamp = 'extern "C" const char* as_source_hash(void) { return "%s"; }\n' % _source_hash()
     if not os.path.exists(stamp_src) or open(stamp_src).read() != stamp:
         open(stamp_src, "w").write(stamp)
-    deps = [os.path.join(CSRC, "common.h"), HEADER]
+    deps = [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith(".h")] + [HEADER]
     hipcc = _hipcc()
     jobs = []
     for s in srcs:

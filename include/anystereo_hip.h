@@ -233,6 +233,31 @@ typedef struct {
   void* out_bs_b;
 } as_conv_desc;
 int as_conv2d(const as_conv_desc* d, void* stream);
+/* The A/B knobs of the dispatch (README: AS_CONV_LEAN, _XCD, _XCD_STAGGER, _LEAN_OFFSET, _KSPLIT_MAX, _DMA, _WIDE, _WIDE64, _SMALL_DMA,
+   _PREFER64).  The process reads them from the environment once, at the first as_conv2d / as_conv2d_plan call. */
+typedef struct {
+  int lean, xcd, xcd_stagger, lean_offset, ksplit_max, dma, wide, wide64, small_dma, prefer64;
+} as_conv_knobs;
+/* What as_conv2d launches for a descriptor: the kernel instantiation, its grid and its schedule parameters. */
+typedef struct {
+  int family;         /* 0: conv_igemm_kernel<KS, TW, epilogue> (precision 0); 1: conv_split_kernel<KS, TW, BN, epilogue, NSUB, S, FAST, LEAN> */
+  int KS, TW, BN;     /* kernel size; tile width in pixels (tile = 64 / TW rows at family 0, 128 / TW at family 1); output channels per block */
+  int NSUB, S;        /* pixel tiles per block (2: the 256-pixel "wide" blocks); stride */
+  int FAST, LEAN;     /* the one-MFMA fp16 variant (as_set_fast16); two 4-wave blocks per CU instead of one 8-wave block */
+  int epilogue;       /* of the kernel: the descriptor's AS_EPI_*, or 3 = raw partial sums of a K slice when ksplit > 1 */
+  int finish, finish_epilogue;  /* finish != 0 (ksplit > 1): a conv_finish_kernel<finish_epilogue> launch of finish_grid x 256 threads follows */
+  int ksplit;         /* K slices = blocks per output tile */
+  int tiles_x, tiles_y, n_tiles, chunks;  /* pixel tiles of the output plane; channel tiles (both convolutions of a fused dual launch); K chunks */
+  int H, W, Hi, Wi;   /* output and input plane as the kernel sees them (1x1: flattened to one row) */
+  int all_bs, xcd_map, stagger, lean_offset;  /* all-DMA operand staging; XCD-aware block order; start delays (AS_CONV_XCD_STAGGER, AS_CONV_LEAN_OFFSET) */
+  int dual;           /* 0: not a dual launch; 1: both convolutions fused in this grid; 2: two calls, one after the other (precision 0, or a
+                         K split) - then the other fields are the first call's */
+  int block, lds;     /* threads per block; dynamic LDS bytes */
+  int64_t grid, finish_grid;  /* blocks */
+} as_conv_plan;
+/* The plan as_conv2d would execute for *d under *knobs (NULL: the process's knobs).  Runs as_conv2d's validation and returns its codes;
+   host arithmetic only: no data pointer is dereferenced, nothing is launched, no device is needed. */
+int as_conv2d_plan(const as_conv_desc* d, const as_conv_knobs* knobs, as_conv_plan* out);
 /* floats of split-K scratch worth passing in as_conv_desc.ws for this problem (0: the problem is large enough) */
 int64_t as_conv_ws_elems(int B, int Cout, int H, int W);
 /* weight [Cout,Cin,KS,KS] (nn.Conv2d layout) -> wpack; returns the element count needed when wpack==NULL */

@@ -141,7 +141,7 @@ def test_abi_argument_validation_without_gpu():
         import __graft_entry__ as ge
         ge.build()
     lib = _lib.load()
-    assert lib.as_abi_version() == 37
+    assert lib.as_abi_version() == 38
     buf = (ctypes.c_double * 64)()
     base = ctypes.addressof(buf)
     p, null = ctypes.c_void_p(base), ctypes.c_void_p(0)

@@ -227,7 +227,7 @@ def test_abi_argument_validation_without_gpu():
         import __graft_entry__ as ge
         ge.build()
     lib = _lib.load()
-    assert lib.as_abi_version() == 37
+    assert lib.as_abi_version() == 38
     buf = (ctypes.c_double * 64)()
     p, null = ctypes.c_void_p(ctypes.addressof(buf)), ctypes.c_void_p(0)
     inf = float("inf")

@@ -2452,6 +2452,96 @@ def test_dgrad_pack_equals_transposed_flipped_copy(cout, cin, ks):
         ops.set_precision(prev)
 
 
+# name, precision, (B, H, W, Cin, Cout), conv2d form, the instantiation the default knobs select: family (1 = conv_split_kernel),
+# KS, TW, BN, kernel epilogue (3 = K-split partial sums), NSUB, S, FAST, LEAN.  Each shape is the smallest that selects its
+# instantiation: Cin 16 is a single K chunk, which keeps a small map from splitting K.
+_DISPATCH_CASES = [
+    ("tw16_bn64", "split", (1, 9, 14, 16, 64), {}, (1, 3, 16, 64, 0, 1, 1, 0, 0)),
+    ("tw32_bn64", "split", (1, 4, 60, 16, 64), {}, (1, 3, 32, 64, 0, 1, 1, 0, 0)),
+    # 255 blocks of 128 channels: no room for a K split, and two rounds of wide blocks
+    ("tw16_bn128", "split", (17, 8, 80, 32, 384), {}, (1, 3, 16, 128, 0, 1, 1, 0, 0)),
+    ("tw32_bn128", "split", (17, 4, 160, 32, 384), {}, (1, 3, 32, 128, 0, 1, 1, 0, 0)),
+    ("wide", "split", (1, 16, 17, 16, 128), {}, (1, 3, 16, 64, 0, 2, 1, 0, 0)),
+    ("lean", "split", (1, 136, 240, 16, 256), {"blocked": True}, (1, 3, 16, 64, 0, 2, 1, 0, 1)),
+    ("ksplit", "split", (1, 17, 30, 128, 128), {}, (1, 3, 32, 128, 3, 1, 1, 0, 0)),
+    ("stride2", "split", (1, 9, 35, 16, 32), {"stride": 2}, (1, 3, 16, 64, 0, 1, 2, 0, 0)),
+    ("1x1_bn64", "split", (1, 3, 50, 36, 64), {"ks": 1}, (1, 1, 128, 64, 0, 1, 1, 0, 0)),
+    ("1x1_bn128", "split", (1, 1, 300, 32, 128), {"ks": 1}, (1, 1, 128, 128, 0, 1, 1, 0, 0)),
+    ("relu_taps", "split", (1, 24, 40, 16, 64), {"taps": True}, (1, 3, 16, 64, 4, 1, 1, 0, 0)),
+    ("dual_fused", "split", (1, 9, 14, 16, 64), {"dual": 1}, (1, 3, 16, 64, 0, 1, 1, 0, 0)),
+    ("dual_sequential", "split", (1, 9, 14, 64, 64), {"dual": 2}, (1, 3, 16, 64, 3, 1, 1, 0, 0)),
+    ("fp32_tw8", "fp32", (1, 9, 8, 20, 40), {}, (0, 3, 8, 64, 0, 1, 1, 0, 0)),
+    ("fp32_tw16", "fp32", (1, 5, 16, 20, 40), {}, (0, 3, 16, 64, 0, 1, 1, 0, 0)),
+    ("fp32_tw32", "fp32", (1, 2, 33, 20, 40), {}, (0, 3, 32, 64, 0, 1, 1, 0, 0)),
+]
+
+
+def _planned_kernels(plan):
+    """The names of the kernels a plan (ops.conv_plan) says as_conv2d launches, in launch order."""
+    if plan["family"]:
+        main = "conv_split_kernel<%d, %d, %d, %d, %d, %d, %s, %s>" % (
+            plan["KS"], plan["TW"], plan["BN"], plan["epilogue"], plan["NSUB"], plan["S"], str(bool(plan["FAST"])).lower(), str(bool(plan["LEAN"])).lower())
+    else:
+        main = "conv_igemm_kernel<%d, %d, %d>" % (plan["KS"], plan["TW"], plan["epilogue"])
+    one = [main] + (["conv_finish_kernel<%d>" % plan["finish_epilogue"]] if plan["finish"] else [])
+    return one * (2 if plan["dual"] == 2 else 1)  # a dual launch as two calls: the second has the first's shape
+
+
+def test_conv_dispatch_runs_the_planned_kernel():
+    """as_conv2d's dispatch and the planner that mirrors it (csrc/conv_plan.h), under the default knobs, for a shape per
+    instantiation family: ops.conv_plan names the expected instantiation; the kernels as_conv2d really launches — their names and
+    order, read from the profiler's kernel trace — are the plan's, K-split finish launches and the two calls of an unfused dual
+    launch included; and the result of ops.conv2d is the fp64 convolution's (+ the epilogue in torch) within the conv parity tests'
+    1e-5 (RELU_TAPS: 2e-5, through tap_shift_sum, as test_conv_relu_taps_epilogue)."""
+    import re
+
+    from torch.profiler import ProfilerActivity, profile
+
+    from anystereo import _lib as Lb, ops
+    prev = ops.get_precision()
+    tuple_of = ("family", "KS", "TW", "BN", "epilogue", "NSUB", "S", "FAST", "LEAN")
+    expected = []
+    try:
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for name, prec, (b, h, w, cin, cout), form, want in _DISPATCH_CASES:
+                ops.set_precision(prec)
+                ks, stride, dual = form.get("ks", 3), form.get("stride", 1), form.get("dual", 0)
+                plan = ops.conv_plan(dict(B=b, H=h, W=w, Cin=cin, Cout=cout, KS=ks, precision=int(prec == "split"), stride=stride, dual=dual,
+                                          blocked=form.get("blocked"), epilogue=Lb.EPI_RELU_TAPS if form.get("taps") else Lb.EPI_LINEAR,
+                                          act=Lb.ACT_RELU))
+                assert tuple(plan[f] for f in tuple_of) == want and plan["dual"] == dual, (name, plan)
+                assert (plan["ksplit"] > 1) == (want[4] == 3) == bool(plan["finish"]), (name, plan)
+                expected += [(name, k) for k in _planned_kernels(plan)]
+                x = U((b, cin, h, w), 700, -2, 2)
+                wt, bias = U((cout, cin, ks, ks), 701) * (3.0 / (cin * ks * ks)) ** 0.5, U((cout,), 702) * 0.1
+                pk = ops.PackedConv().get([wt.to(DEV)], [bias.to(DEV)])
+                ref = torch.nn.functional.conv2d(x.double(), wt.double(), bias.double(), stride=stride, padding=ks // 2).relu()
+                src = x.to(DEV)
+                if form.get("blocked"):
+                    hi = src.half()
+                    lo = ((src - hi.float()) * 2048.0).half()
+                    src = ops.BS8(torch.stack([hi, lo], 1).view(b, 2, cin // 8, 8, h, w).permute(0, 1, 2, 4, 5, 3).contiguous(), cin)
+                if form.get("taps"):
+                    w2, b2 = U((1, cout, 3, 3), 703) * 0.05, U((1,), 704)
+                    taps = ops.conv2d([src], pk, act=Lb.ACT_RELU, epilogue=Lb.EPI_RELU_TAPS, tap_w=w2[0].reshape(cout, 9).contiguous().to(DEV))
+                    close(ops.tap_shift_sum(taps, b2.to(DEV)), _ref_conv(ref, w2, b2, 1), 2e-5, 2e-5, name)
+                elif dual:
+                    x2, wt2 = U((b, cin, h, w), 705, -2, 2), U((cout, cin, ks, ks), 706) * (3.0 / (cin * ks * ks)) ** 0.5
+                    pk2 = ops.PackedConv().get([wt2.to(DEV)], [None])
+                    out = torch.empty((b, 2 * cout, h, w), device=DEV)
+                    ops.conv2d([src], pk, act=Lb.ACT_RELU, out=out, dual={"src": x2.to(DEV), "pack": pk2, "out_coff": cout})
+                    close(out[:, :cout], ref, 1e-5, 1e-5, name)
+                    close(out[:, cout:], _ref_conv(x2, wt2, None, ks // 2).relu(), 1e-5, 1e-5, name + " (second)")
+                else:
+                    close(ops.conv2d([src], pk, act=Lb.ACT_RELU, stride=stride), ref, 1e-5, 1e-5, name)
+            torch.cuda.synchronize()
+    finally:
+        ops.set_precision(prev)
+    launched = sorted((e.time_range.start, m.group(0)) for e in prof.events()
+                      for m in [re.search(r"conv_(split|igemm|finish)_kernel<[^>]*>", e.name)] if m)
+    assert [k for _, k in launched] == [k for _, k in expected], list(zip(expected, [k for _, k in launched]))
+
+
 KNOB_SETS = [
     {"AS_CONV_LEAN": "0", "AS_CONV_XCD": "0", "AS_CONV_DMA": "0", "AS_POOL2X_EVEN": "0", "AS_LOOKUP_DIRECT": "0"},
     {"AS_CONV_XCD": "1", "AS_CONV_LEAN": "3", "AS_CONV_KSPLIT_MAX": "1", "AS_CONV_WIDE": "0", "AS_CONV_WIDE64": "0", "AS_CONV_SMALL_DMA": "0", "AS_LOOKUP_DIRECT": "2"},

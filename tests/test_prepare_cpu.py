@@ -137,7 +137,7 @@ def test_abi_argument_validation_without_gpu():
     65535 -> AS_ERR_BAD_SHAPE (-2); all before any launch, so no GPU is needed."""
     from anystereo import _lib
     lib = _lib.load()
-    assert lib.as_abi_version() == 37
+    assert lib.as_abi_version() == 38
     buf = (ctypes.c_float * 64)()
     p, null = ctypes.c_void_p(ctypes.addressof(buf)), ctypes.c_void_p(0)
     ok = (1, 8, 8, 4, 4, 0, 0, 0, 0)  # B, H, W, h_lr, w_lr, pads

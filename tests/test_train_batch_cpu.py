@@ -209,7 +209,7 @@ def test_abi_argument_validation_without_gpu():
     below are never dereferenced on the device."""
     from anystereo import _lib
     lib = _lib.load()
-    assert lib.as_abi_version() == 37
+    assert lib.as_abi_version() == 38
     buf = (ctypes.c_float * 64)()
     p, null = ctypes.c_void_p(ctypes.addressof(buf)), ctypes.c_void_p(0)
     I = ctypes.c_int

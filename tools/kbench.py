@@ -9,6 +9,8 @@ import sys
 
 ROOT = os.path.abspath(os.path.join(os.path.dirname(__file__), ".."))
 sys.path.insert(0, os.path.join(ROOT, "any-stereo_amd"))
+import ctypes
+
 import torch  # noqa: E402
 
 from anystereo import ops  # noqa: E402
@@ -134,9 +136,28 @@ def main():
         "gru_zr_bs1": lambda: ops.conv2d([x128bs[0], x128[1], x128[2]], pzr, add=ctx, add_coff=0, epilogue=Lb.EPI_GRU_ZR, h=x128[0]),
         "gru_zr": lambda: ops.conv2d(x128, pzr, add=ctx, add_coff=0, epilogue=Lb.EPI_GRU_ZR, h=x128[0]),
     }
+    def plans_of(fn):  # run fn once (the first warm-up call); the plan of every as_conv2d call it makes, so an A/B run says which schedule it timed
+        lib, lines = Lb.load(), []
+        real = lib.as_conv2d
+
+        def spy(desc_ref, stream):
+            p = ops.conv_plan(ctypes.cast(desc_ref, ctypes.POINTER(Lb.ConvDesc)).contents)
+            targs = [p[f] for f in (("KS", "TW", "BN", "epilogue", "NSUB", "S", "FAST", "LEAN") if p["family"] else ("KS", "TW", "epilogue"))]
+            lines.append(f"  plan: {'conv_split_kernel' if p['family'] else 'conv_igemm_kernel'}<{', '.join(map(str, targs))}> grid {p['grid']} x {p['block']}, "
+                         f"LDS {p['lds']}, ksplit {p['ksplit']}" + (f" + finish grid {p['finish_grid']}" if p["finish"] else "")
+                         + ("", ", dual fused", ", dual as two calls")[p["dual"]])
+            return real(desc_ref, stream)
+        lib.as_conv2d = spy  # ops looks the entry up on the loaded library at every call
+        try:
+            fn()
+        finally:
+            lib.as_conv2d = real
+        return lines
+
     for k in a.kernels:
         fn = fns[k]
-        for _ in range(3):
+        plan_lines = plans_of(fn)
+        for _ in range(2):
             fn()
         torch.cuda.synchronize()
         s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -163,6 +184,7 @@ def main():
             e.record()
         torch.cuda.synchronize()
         print(f"{k}: {s.elapsed_time(e) / a.reps * 1e3:.2f} us/launch (cfg {a.cfg}, precision {ops.get_precision()})")
+        print("\n".join(plan_lines))
 
 
 if __name__ == "__main__":
