@@ -960,7 +960,12 @@ def conv2d(srcs: Sequence[torch.Tensor], pack: PackedConv, act: int = L.ACT_NONE
         _req(tap_w, "tap_w")
         if tuple(tap_w.shape) != (cout, 9) or not pack.split or pack.ks != 3 or stride != 1:
             raise RuntimeError("conv2d(RELU_TAPS): tap_w must be [Cout, 9]; 3x3 split-precision convolution at stride 1")
-        out = torch.empty((b, (cout + 63) // 64 * 9, hh, ww), device=dev, dtype=torch.float32)
+        planes = (cout + 63) // 64 * 9
+        if out is None:
+            out = torch.empty((b, planes, hh, ww), device=dev, dtype=torch.float32)
+        _req(out, "out")
+        if tuple(out.shape) != (b, planes, hh, ww):
+            raise RuntimeError("conv2d(RELU_TAPS): out must be [B, ceil(Cout/64)*9, H, W]")
         d.out, d.tap_w = out.data_ptr(), tap_w.data_ptr()
     elif epilogue == L.EPI_LINEAR and bs_only:
         out = None

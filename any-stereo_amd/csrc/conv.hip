@@ -2142,7 +2142,9 @@ int as_conv2d(const as_conv_desc* d, void* stream) {
   AS_REQUIRE(stride == 1 || (stride == 2 && split && d->KS == 3 && epi == AS_EPI_LINEAR), AS_ERR_BAD_ARG,
              "conv2d: stride=%d (stride 2: 3x3, split precision, LINEAR epilogue only)", stride);
   if (split) {
-    const int bn = (p.Cout_pad % 128 == 0) ? 128 : 64;
+    // 128-channel tiles where they tile the padded Cout.  GRU_ZR: a tile must lie inside one half of the channels (z | r: the
+    // epilogue picks its output tensor per block), so Cout / 2 has to be a multiple of the tile too — else 64-channel tiles
+    const int bn = (p.Cout_pad % 128 == 0 && !(epi == AS_EPI_GRU_ZR && d->Cout % 256 != 0)) ? 128 : 64;
     p.n_tiles = p.Cout_pad / bn;
     AS_REQUIRE((long long)d->H * d->W < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: plane too large");
     p.Hi = d->H;

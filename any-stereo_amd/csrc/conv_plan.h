@@ -147,7 +147,8 @@ inline int conv_plan(const as_conv_desc& d, const ConvKnobs& k, int fast16, Conv
     return AS_OK;
   }
 
-  const int bn = (cout_pad % 128 == 0) ? 128 : 64;
+  // GRU_ZR: a channel tile lies inside one half of the channels (z | r), so 128-channel tiles need Cout / 2 % 128 == 0 as well
+  const int bn = (cout_pad % 128 == 0 && !(d.epilogue == AS_EPI_GRU_ZR && d.Cout % 256 != 0)) ? 128 : 64;
   pl.chunks = (d.Cin + kSplitKC - 1) / kSplitKC;
   {
     bool all = true;

@@ -165,6 +165,8 @@ def descriptor(lib_mod, c, ws_elems):
         d.dual, d.src2, d.src2_bs, d.wpack2 = 1, FAKE * 16, 1 if c["dual"] == "bs" else 0, FAKE * 17
         if c["dual"] == "sep":
             d.out_b = FAKE * 18
+            if c["out_bs"]:
+                d.out_bs_b = FAKE * 20
         else:
             d.out_coff2, d.out_bs_coff2 = c["Cout"], c["Cout"] if c["out_bs"] else 0
     if c["ws"] and c["prec"] == 1 and c["stride"] == 1 and ws_elems > 0:

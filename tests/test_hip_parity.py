@@ -2476,15 +2476,7 @@ _DISPATCH_CASES = [
 ]
 
 
-def _planned_kernels(plan):
-    """The names of the kernels a plan (ops.conv_plan) says as_conv2d launches, in launch order."""
-    if plan["family"]:
-        main = "conv_split_kernel<%d, %d, %d, %d, %d, %d, %s, %s>" % (
-            plan["KS"], plan["TW"], plan["BN"], plan["epilogue"], plan["NSUB"], plan["S"], str(bool(plan["FAST"])).lower(), str(bool(plan["LEAN"])).lower())
-    else:
-        main = "conv_igemm_kernel<%d, %d, %d>" % (plan["KS"], plan["TW"], plan["epilogue"])
-    one = [main] + (["conv_finish_kernel<%d>" % plan["finish_epilogue"]] if plan["finish"] else [])
-    return one * (2 if plan["dual"] == 2 else 1)  # a dual launch as two calls: the second has the first's shape
+from _conv_cases import planned_kernels as _planned_kernels  # noqa: E402  (shared with test_conv_instantiations_gpu.py)
 
 
 def test_conv_dispatch_runs_the_planned_kernel():
