@@ -92,6 +92,9 @@ SIGNATURES = {
     "as_disparity_regression": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "as_conv2d": (_i, [C.POINTER(ConvDesc), _vp]),
     "as_conv2d_plan": (_i, [C.POINTER(ConvDesc), C.POINTER(ConvKnobs), C.POINTER(ConvPlan)]),
+    "as_conv1x1_stream_ok": (_i, [C.POINTER(ConvDesc)]),
+    "as_conv1x1_stream": (_i, [C.POINTER(ConvDesc), _vp]),
+    "as_pointwise_split_overflow": (C.c_uint, [_i]),
     "as_conv_ws_elems": (C.c_int64, [_i, _i, _i, _i]),
     "as_conv_pack_size": (C.c_int64, [_i, _i, _i]),
     "as_conv_pack_weights": (_i, [_vp, _vp, _i, _i, _i, _vp]),

@@ -42,6 +42,8 @@ def conv2d_plain(mod: nn.Module, conv: nn.Module, x: torch.Tensor) -> torch.Tens
     if conv2d_hip_ok(conv):
         packs = mod.__dict__.setdefault("_hip_packs", {})
         pk = packs.setdefault(id(conv), ops.PackedConv())
+        if conv.kernel_size == (1, 1) and conv.stride == (1, 1):  # pointwise: the streaming kernel where it is routed there
+            return ops.conv1x1([x.contiguous()], pk.get([conv.weight], [conv.bias]))
         return ops.conv2d([x.contiguous()], pk.get([conv.weight], [conv.bias]), stride=conv.stride[0])
     if (isinstance(conv, nn.Conv2d) and conv.kernel_size == (1, 1) and conv.padding == (0, 0) and conv.groups == 1
             and conv.stride[0] == conv.stride[1] and conv.stride[0] > 1):
@@ -49,7 +51,7 @@ def conv2d_plain(mod: nn.Module, conv: nn.Module, x: torch.Tensor) -> torch.Tens
         packs = mod.__dict__.setdefault("_hip_packs", {})
         pk = packs.setdefault(id(conv), ops.PackedConv())
         st = conv.stride[0]
-        return ops.conv2d([x[:, :, ::st, ::st].contiguous()], pk.get([conv.weight], [conv.bias]))
+        return ops.conv1x1([x[:, :, ::st, ::st].contiguous()], pk.get([conv.weight], [conv.bias]))
     return conv(x)
 
 
@@ -270,13 +272,14 @@ class _ConvNormAct(nn.Module):
             b_, _, d_, h_, w_ = xs[0].shape
             pk = self.__dict__.setdefault("_pk_fold", ops.PackedConv())
             pack = pk.get_folded(c, norm) if norm is not None else pk.get([c.weight], [c.bias])
-            y = ops.conv2d([t.contiguous().view(b_, t.shape[1], 1, d_ * h_ * w_) for t in xs], pack,
-                           act=L.ACT_LEAKY if self.relu else L.ACT_NONE)
+            y = ops.conv1x1([t.contiguous().view(b_, t.shape[1], 1, d_ * h_ * w_) for t in xs], pack,
+                            act=L.ACT_LEAKY if self.relu else L.ACT_NONE)
             return y.view(b_, c.out_channels, d_, h_, w_)
         if ok and xs[0].dim() == 4 and _plain_instance_norm(norm) and conv2d_hip_ok(c) and c.stride == (1, 1):
             packs = self.__dict__.setdefault("_hip_packs", {})
             pk = packs.setdefault(id(c), ops.PackedConv())
-            y = ops.conv2d([t.contiguous() for t in xs], pk.get([c.weight], [c.bias]))
+            conv = ops.conv1x1 if c.kernel_size == (1, 1) else ops.conv2d
+            y = conv([t.contiguous() for t in xs], pk.get([c.weight], [c.bias]))
             return ops.instance_norm_act(y, norm.eps, L.ACT_LEAKY if self.relu else L.ACT_NONE)
         return self(torch.cat(xs, 1))
 
@@ -302,13 +305,15 @@ class _ConvNormAct(nn.Module):
             pk = self.__dict__.setdefault("_pk_fold", ops.PackedConv())
             if x.dim() == 4 and conv2d_hip_ok(c):
                 pack = pk.get_folded(c, norm) if norm is not None else pk.get([c.weight], [c.bias])
+                if c.kernel_size == (1, 1) and c.stride == (1, 1):
+                    return ops.conv1x1([x.contiguous()], pack, act=act)
                 return ops.conv2d([x.contiguous()], pack, act=act, stride=c.stride[0])
             if (x.dim() == 5 and c.kernel_size == (1, 1, 1) and c.stride == (1, 1, 1) and c.padding == (0, 0, 0)
                     and c.dilation == (1, 1, 1) and c.groups == 1 and x.shape[2] * x.shape[3] * x.shape[4] < 2 ** 31):
                 # 1x1x1: a pointwise map over D*H*W = the 1x1 kernel on the flattened volume
                 b_, ci, d_, h_, w_ = x.shape
                 pack = pk.get_folded(c, norm) if norm is not None else pk.get([c.weight], [c.bias])
-                y = ops.conv2d([x.contiguous().view(b_, ci, 1, d_ * h_ * w_)], pack, act=act)
+                y = ops.conv1x1([x.contiguous().view(b_, ci, 1, d_ * h_ * w_)], pack, act=act)
                 return y.view(b_, c.out_channels, d_, h_, w_)
         if fused_ok(x, self) and x.dim() == 4 and _plain_instance_norm(norm):
             # conv (library kernel where it applies, else MIOpen) -> fused InstanceNorm + LeakyReLU
@@ -472,7 +477,7 @@ class FeatureAtt(nn.Module):
         gates of a pass on a branch of their own beside the cost aggregation (`early`, set per forward by the model)."""
         c = self.feat_att[1]  # 1x1 + bias with the sigmoid in the epilogue
         pk = self.__dict__.setdefault("_pk_gate", ops.PackedConv())
-        return ops.conv2d([self.feat_att[0](feat).contiguous()], pk.get([c.weight], [c.bias]), act=L.ACT_SIGMOID)
+        return ops.conv1x1([self.feat_att[0](feat).contiguous()], pk.get([c.weight], [c.bias]), act=L.ACT_SIGMOID)
 
     early = None  # (gate tensor, event recorded behind it on the branch stream) for the next forward() call, or None
 

@@ -101,7 +101,7 @@ class ResidualBlock(nn.Module):
                 # MIOpen (90 -> ~35 us for 64 -> 96 at 544x960)
                 st = ds.stride[0]
                 xs = x if st == 1 else x[:, :, ::st, ::st].contiguous()
-                x = ops.conv2d([xs], self._pkd.get_folded(ds, self.downsample[1]))
+                x = ops.conv1x1([xs], self._pkd.get_folded(ds, self.downsample[1]))
             else:
                 w, b = self._fd.get(ds, self.downsample[1])
                 x = nn.functional.conv2d(x, w, b, ds.stride)
@@ -327,7 +327,7 @@ class _DSConv(nn.Module):
             x = x.contiguous()
             w, b = self._fdw.get(self.conv_dw, self.bn1)
             y = ops.dwconv3x3(x, w, b, self.conv_dw.stride[0], L.ACT_RELU6)
-            return ops.conv2d([y], self._pk.get_folded(self.conv_pw, self.bn2), add=x if self.res else None)
+            return ops.conv1x1([y], self._pk.get_folded(self.conv_pw, self.bn2), add=x if self.res else None)
         y = nn.functional.relu6(self.bn1(G.module_dwconv(self.conv_dw, x)))  # training: own forward / dgrad / wgrad kernels
         y = self.bn2(self.conv_pw(y))
         return x + y if self.res else y
@@ -366,10 +366,10 @@ class _InvRes(nn.Module):
         if _fused_ok(x, self):
             # pw (+bn1, ReLU6) and pwl (+bn3, + skip) on the implicit-GEMM kernel, dw (+bn2, ReLU6) on the direct one
             x = x.contiguous()
-            y = ops.conv2d([x], self._pk1.get_folded(self.conv_pw, self.bn1), act=L.ACT_RELU6)
+            y = ops.conv1x1([x], self._pk1.get_folded(self.conv_pw, self.bn1), act=L.ACT_RELU6)
             w, b = self._fdw.get(self.conv_dw, self.bn2)
             y = ops.dwconv3x3(y, w, b, self.conv_dw.stride[0], L.ACT_RELU6)
-            return ops.conv2d([y], self._pk3.get_folded(self.conv_pwl, self.bn3), add=x if self.res else None)
+            return ops.conv1x1([y], self._pk3.get_folded(self.conv_pwl, self.bn3), add=x if self.res else None)
         y = nn.functional.relu6(self.bn1(self.conv_pw(x)))
         y = nn.functional.relu6(self.bn2(G.module_dwconv(self.conv_dw, y)))
         y = self.bn3(self.conv_pwl(y))

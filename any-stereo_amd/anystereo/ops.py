@@ -1096,6 +1096,85 @@ def conv2d_plain(x: torch.Tensor, pack: "PackedConv", act: int = L.ACT_NONE) -> 
     return out
 
 
+def pw_stream_route(cin: int, cout: int, pixels: int) -> bool:
+    """Whether a 1x1 convolution Cin -> Cout over `pixels` = B*H*W positions goes to the streaming kernel (csrc/pointwise.hip)
+    where as_conv1x1_stream_ok accepts it.  A pure function of the shape: the shapes at which the streaming kernel measured
+    faster stand-alone than as_conv2d by more than the spread between repeats (profiles/pointwise_stream_kbench.txt)."""
+    # measured: every pre-loop shape that as_conv2d does not split over K — 2 040 to 261 120 positions, up to 192 channels on
+    # either side — ran 1.10x (128 -> 128 at 68x120) to 4.2x (16 -> 96 at 2x272x480) faster, each outside the repeats' ranges;
+    # nothing lost.  Shapes outside that envelope were not measured and stay on as_conv2d.
+    return pixels >= 2040 and cin <= 192 and cout <= 192
+
+
+def _pw_stream_mode() -> str:
+    """ANYSTEREO_PW_STREAM: "1" (default) the measured shapes of pw_stream_route, "0" nothing (everything through conv2d, for
+    A/B runs), "all" whatever as_conv1x1_stream_ok accepts (kernel benchmarks and tests)."""
+    return os.environ.get("ANYSTEREO_PW_STREAM", "1")
+
+
+def conv1x1(srcs: Sequence[torch.Tensor], pack: PackedConv, act: int = L.ACT_NONE, add: Optional[torch.Tensor] = None,
+            add_coff: int = 0, out: Optional[torch.Tensor] = None, out_coff: int = 0, h: Optional[torch.Tensor] = None,
+            force: bool = False):
+    """conv2d(srcs, pack, act, add, add_coff, out, out_coff, h=h) for a 1x1 convolution with the LINEAR epilogue at stride 1, on the
+    streaming kernel (as_conv1x1_stream: bit-identical results, every source plane read once) where the shape is routed there
+    (pw_stream_route) and as_conv1x1_stream_ok accepts the descriptor; on conv2d otherwise.
+    force: skip the routing rule and raise where the streaming kernel cannot take the descriptor (tests, kernel benchmarks)."""
+    mode = "all" if force else _pw_stream_mode()
+    fp32_srcs = all(isinstance(s, torch.Tensor) for s in srcs)
+    b, _, hh, ww = srcs[0].shape
+    if not force and (mode == "0" or not pack.split or pack.ks != 1 or not fp32_srcs
+                      or (mode != "all" and not pw_stream_route(pack.cin, pack.cout, b * hh * ww))):
+        return conv2d(srcs, pack, act=act, add=add, add_coff=add_coff, out=out, out_coff=out_coff, h=h)
+    lib = L.load()
+    d = L.ConvDesc()
+    cin = 0
+    if len(srcs) > L.AS_MAX_SRCS:
+        raise RuntimeError(f"conv1x1: at most {L.AS_MAX_SRCS} sources")
+    for i, s in enumerate(srcs):
+        _req(s, f"src[{i}]")
+        if s.shape[0] != b or tuple(s.shape[2:]) != (hh, ww):
+            raise RuntimeError(f"conv1x1: src[{i}] shape {tuple(s.shape)} does not match {(b, '*', hh, ww)}")
+        d.src[i], d.src_c[i] = s.data_ptr(), s.shape[1]
+        cin += s.shape[1]
+    if cin != pack.cin:
+        raise RuntimeError(f"conv1x1: sources hold {cin} channels but the weights expect {pack.cin}")
+    cout, dev = pack.cout, srcs[0].device
+    d.n_src = len(srcs)
+    d.wpack = pack.wpack.data_ptr()
+    d.bias = 0 if pack.bias is None else pack.bias.data_ptr()
+    if add is not None:
+        _req(add, "add")
+        if add.shape[0] != b or tuple(add.shape[2:]) != (hh, ww):
+            raise RuntimeError("conv1x1: add shape mismatch")
+        d.add, d.add_ctot, d.add_coff = add.data_ptr(), add.shape[1], add_coff
+    if h is not None:
+        _req(h, "h")
+        if tuple(h.shape) != (b, cout, hh, ww):
+            raise RuntimeError("conv1x1: residual h must be [B,Cout,H,W]")
+        d.h = h.data_ptr()
+    d.B, d.H, d.W, d.Cin, d.Cout, d.KS = b, hh, ww, cin, cout, pack.ks
+    d.stride, d.act, d.epilogue, d.precision = 1, act, L.EPI_LINEAR, 1 if pack.split else 0
+    # the planner's view of the call conv2d would make: it hands as_conv2d split-K scratch on small maps (never dereferenced here)
+    n_ws = lib.as_conv_ws_elems(b, cout, hh, ww) if pack.split else 0
+    if n_ws > 0:
+        d.ws, d.ws_elems = 1 << 20, n_ws
+    d.out, d.out_ctot = (1 << 20) if out is None else out.data_ptr(), cout if out is None else out.shape[1]
+    d.out_coff = out_coff
+    if not lib.as_conv1x1_stream_ok(C.byref(d)):
+        if force:
+            raise RuntimeError("conv1x1(force): as_conv1x1_stream_ok rejects this convolution")
+        return conv2d(srcs, pack, act=act, add=add, add_coff=add_coff, out=out, out_coff=out_coff, h=h)
+    if out is None:
+        out = torch.empty((b, cout, hh, ww), device=dev, dtype=torch.float32)
+    _req(out, "out")
+    if out.shape[0] != b or tuple(out.shape[2:]) != (hh, ww):
+        raise RuntimeError("conv1x1: out shape mismatch")
+    d.out, d.out_ctot, d.ws, d.ws_elems = out.data_ptr(), out.shape[1], 0, 0
+    with _guard(dev):
+        L.check(lib.as_conv1x1_stream(C.byref(d), _stream()), "conv1x1_stream")
+    return out
+
+
 _TAPMAJOR = {}  # (data_ptr, version, device) of a [Cout,1,7,7] weight -> its [49,Cout] transpose
 
 
@@ -2063,4 +2142,4 @@ def split_overflow_count(reset: bool = True) -> int:
     reference's; switch to `set_precision("fp32")` for such data.  Synchronises the device (diagnostics, tests, bench)."""
     lib, r = L.load(), 1 if reset else 0
     return sum(int(f(r)) for f in (lib.as_liif_split_overflow, lib.as_lookup_split_overflow, lib.as_conv_split_overflow,
-                                   lib.as_volumes_split_overflow))
+                                   lib.as_volumes_split_overflow, lib.as_pointwise_split_overflow))

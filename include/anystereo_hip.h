@@ -258,6 +258,21 @@ typedef struct {
 /* The plan as_conv2d would execute for *d under *knobs (NULL: the process's knobs).  Runs as_conv2d's validation and returns its codes;
    host arithmetic only: no data pointer is dereferenced, nothing is launched, no device is needed. */
 int as_conv2d_plan(const as_conv_desc* d, const as_conv_knobs* knobs, as_conv_plan* out);
+/* Streaming 1x1 convolution (pointwise.hip) for the memory-bound pointwise layers: the arithmetic of as_conv2d on the same
+   descriptor — same operand split, same MFMA products in the same K order, same epilogue — with every source plane read once
+   from fp32 NCHW straight into registers, so the results are BIT-IDENTICAL to as_conv2d's.
+   as_conv1x1_stream_ok: 1 when the descriptor can take it, else 0.  Host arithmetic only (no device).  It can when the descriptor
+     passes as_conv2d's validation and: precision 1 (split); KS 1; stride 0 | 1; AS_EPI_LINEAR; no dual launch; no blocked source,
+     no blocked result (out_bs / bs_only); as_set_fast16 off; every source but the last holds a multiple of 16 channels;
+     as_conv2d_plan gives ksplit == 1 for it (a K-split launch sums its slabs in another order); and the shape is inside the
+     kernel's limits:  Cout <= 64 (any Cin), or Cin <= 128 with a weight image of at most 80 KB in LDS (n * 64 * ceil64(Cout) +
+     4 * ceil64(Cout) bytes, n = ceil(Cin / 16) rounded up to 1, 2, 3, 4, 6 or 8);  H * W <= 2^24;
+     ceil32(Cout) * H * W * 4 < 0x7FFFFFF0;  B * ceil(H * W / 128) < 2^31.
+   as_conv1x1_stream: runs it; as_conv2d's codes for what as_conv2d rejects, AS_ERR_BAD_ARG (and no launch) where _ok gives 0.
+   as_pointwise_split_overflow: as_conv_split_overflow for this kernel's operand split. */
+int as_conv1x1_stream_ok(const as_conv_desc* d);
+int as_conv1x1_stream(const as_conv_desc* d, void* stream);
+unsigned as_pointwise_split_overflow(int reset);
 /* floats of split-K scratch worth passing in as_conv_desc.ws for this problem (0: the problem is large enough) */
 int64_t as_conv_ws_elems(int B, int Cout, int H, int W);
 /* weight [Cout,Cin,KS,KS] (nn.Conv2d layout) -> wpack; returns the element count needed when wpack==NULL */
