@@ -24,6 +24,16 @@ int fail(int code, const char* fmt, ...) {
   return code;
 }
 
+unsigned read_reset_counter(const void* symbol, int reset) {
+  unsigned v = 0;
+  if (hipMemcpyFromSymbol(&v, symbol, sizeof(v)) != hipSuccess) return 0xFFFFFFFFu;
+  if (reset && v) {
+    const unsigned z = 0;
+    (void)hipMemcpyToSymbol(symbol, &z, sizeof(z));
+  }
+  return v;
+}
+
 static int g_precision = -1;
 int precision_mode() {
   if (g_precision < 0) {

@@ -8,26 +8,12 @@
 #include <cstdlib>
 
 #include "common.h"
+#include "split.h"
 
 namespace {
 
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-
-__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff, unsigned soff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, (int)soff, 0));
-}
-
-__device__ __forceinline__ float act_apply(float v, int act) {
-  switch (act) {
-    case AS_ACT_RELU: return fmaxf(v, 0.f);
-    case AS_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-    case AS_ACT_TANH: return tanhf(v);
-    case AS_ACT_RELU6: return fminf(fmaxf(v, 0.f), 6.f);
-    case AS_ACT_LEAKY: return v >= 0.f ? v : 0.01f * v;
-    case AS_ACT_GELU: return 0.5f * v * (1.f + erff(v * 0.70710678118654752440f));
-    default: return v;
-  }
-}
+using as::bload;
+using as::f32x2;
 
 constexpr unsigned kOOB = 0x70000000u;  // lane sentinel: stays out of range after adding any in-tensor scalar offset
 
@@ -88,7 +74,7 @@ __global__ __launch_bounds__(256) void dwconv3x3_kernel(const float* __restrict_
       const int oy = oy0 + r;
       if (oy < Ho) {
         const long long o = ((long long)bc * Ho + oy) * Wo + ox;
-        float vv = act_apply(acc[r], act);
+        float vv = as::act_apply<true>(acc[r], act);
         if (res) vv += res[o];
         out[o] = vv;
       }
@@ -150,7 +136,7 @@ __global__ __launch_bounds__(256) void conv3x3_few_kernel(const float* __restric
     const long long oplane = (long long)Ho * Wo;
     float* o = out + ((long long)b * Cout + g * CT) * oplane + (long long)oy * Wo + ox;
 #pragma unroll
-    for (int j = 0; j < CT; ++j) o[j * oplane] = act_apply(acc[j], act);
+    for (int j = 0; j < CT; ++j) o[j * oplane] = as::act_apply<true>(acc[j], act);
   }
 }
 
@@ -261,10 +247,10 @@ __global__ __launch_bounds__(256) void conv3d_k3_kernel(const float* __restrict_
         const long long oplane = (long long)Ho * Wo;
         const float* gp = gate + ((long long)b * Cout + g * CT) * oplane + (long long)(oy + n) * Wo + ox;
 #pragma unroll
-        for (int j = 0; j < CT; ++j) o[j * ovol] = act_apply(acc[n][j], act) * gp[j * oplane];
+        for (int j = 0; j < CT; ++j) o[j * ovol] = as::act_apply<true>(acc[n][j], act) * gp[j * oplane];
       } else {
 #pragma unroll
-        for (int j = 0; j < CT; ++j) o[j * ovol] = act_apply(acc[n][j], act);
+        for (int j = 0; j < CT; ++j) o[j * ovol] = as::act_apply<true>(acc[n][j], act);
       }
     }
   }
@@ -338,8 +324,8 @@ __global__ __launch_bounds__(256) void deconv3d_k4s2_kernel(const float* __restr
 #pragma unroll
     for (int j = 0; j < CT; ++j) {
       f32x2 v;
-      v.x = act_apply(a0[j], act);
-      v.y = act_apply(a1[j], act);
+      v.x = as::act_apply<true>(a0[j], act);
+      v.y = as::act_apply<true>(a1[j], act);
       *reinterpret_cast<f32x2*>(o + j * ovol) = v;  // Wo even: 8-B aligned
     }
   }
@@ -395,7 +381,7 @@ __global__ __launch_bounds__(256) void in_apply_kernel(const float* __restrict__
   const double var = fmax(ss / (double)HW - mean * mean, 0.0);
   const float m = (float)mean, rstd = (float)(1.0 / sqrt(var + (double)eps));
   if (i < HW) {
-    float v = act_apply((x[plane * HW + i] - m) * rstd, act);
+    float v = as::act_apply<true>((x[plane * HW + i] - m) * rstd, act);
     if (res) v = fmaxf(v + res[plane * HW + i], 0.f);  // residual tail relu(res + act(IN(x))) (extractor.py:56-62)
     out[plane * HW + i] = v;
   }
@@ -426,7 +412,7 @@ __global__ __launch_bounds__(256) void layernorm2d_kernel(const float* __restric
   float* op = out + bi * C * HW + rem;
 #pragma unroll
   for (int c = 0; c < CMAX; ++c)
-    if (c < C) op[(long long)c * HW] = act_apply(w[c] * ((v[c] - mu) * rstd) + b[c], act);
+    if (c < C) op[(long long)c * HW] = as::act_apply<true>(w[c] * ((v[c] - mu) * rstd) + b[c], act);
 }
 
 }  // namespace

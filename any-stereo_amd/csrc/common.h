@@ -14,6 +14,9 @@ constexpr int kWave = 64;
 // Thread-local description of the last failure (as_last_error_string()).
 char* err_buf();
 int fail(int code, const char* fmt, ...);
+// Value of a translation unit's `__device__ unsigned` counter (symbol = HIP_SYMBOL(counter)), zeroed afterwards when
+// `reset` is set; 0xFFFFFFFF when it cannot be read.  Body of every as_*_split_overflow entry.
+unsigned read_reset_counter(const void* symbol, int reset);
 
 inline int check_launch(const char* what) {
   hipError_t e = hipGetLastError();

@@ -23,16 +23,11 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "split.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using f32x4 = __attribute__((ext_vector_type(4))) float;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using half4v = __attribute__((ext_vector_type(4))) _Float16;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using namespace as;  // split.h: vector types, operand split / join, act_apply, bload / bstore
 
 struct ConvParams {
   const float* src[AS_MAX_SRCS];
@@ -99,30 +94,12 @@ template <> struct ConvCfg<1> { static constexpr int KC = 32; };
 constexpr int kBM = 64;  // pixels per block
 constexpr int kBN = 64;  // output channels per block
 
-__device__ __forceinline__ float act_apply(float v, int act) {
-  switch (act) {
-    case AS_ACT_RELU: return fmaxf(v, 0.f);
-    case AS_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-    case AS_ACT_TANH: return tanhf(v);
-    case AS_ACT_RELU6: return fminf(fmaxf(v, 0.f), 6.f);
-    case AS_ACT_LEAKY: return v >= 0.f ? v : 0.01f * v;
-    default: return v;
-  }
-}
-
 // ---- epilogue of one 32(co) x 32(pixel) accumulator tile -----------------------------------------
 // All global operands of the tile (context term, h, z) are fetched up front through raw buffer
 // descriptors whose range covers exactly the block's valid output channels: lanes outside the image
 // (sentinel offset) and channels >= Cout read 0 and their stores are dropped by the hardware range check,
 // so there is not a single branch around a memory operation and one latency is paid per tile, not per
 // element.  Bias comes from an LDS copy made by the caller.
-__device__ __forceinline__ float as_bload(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
-__device__ __forceinline__ void as_bstore(__amdgpu_buffer_rsrc_t r, unsigned off, float v) {
-  __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), r, (int)off, 0, 0);
-}
-
 struct EpiCtx {
   __amdgpu_buffer_rsrc_t r_add, r_out, r_h, r_z, r_bs, r_bsl;
   bool has_add, has_bs, skip_out;
@@ -224,9 +201,9 @@ __device__ __forceinline__ void epi_load(const EpiCtx& e, int col0, int half, un
     const int r = g * 8 + i;
     const int col = col0 + (r & 3) + 8 * (r >> 2) + 4 * half;
     R.off[i] = poff == kOOB ? kOOB : (unsigned)col * e.plane4 + poff;
-    R.av[i] = as_bload(e.r_add, R.off[i]);                         // 0 when there is no add tensor (0 records)
-    if (EPI == AS_EPI_GRU_ZR || EPI == AS_EPI_LINEAR) R.hv[i] = as_bload(e.r_h, R.off[i]);  // 0 records: z half / no residual
-    if (EPI == AS_EPI_GRU_Q) { R.hv[i] = as_bload(e.r_h, R.off[i]); R.zv[i] = as_bload(e.r_z, R.off[i]); }
+    R.av[i] = bload(e.r_add, R.off[i]);                         // 0 when there is no add tensor (0 records)
+    if (EPI == AS_EPI_GRU_ZR || EPI == AS_EPI_LINEAR) R.hv[i] = bload(e.r_h, R.off[i]);  // 0 records: z half / no residual
+    if (EPI == AS_EPI_GRU_Q) { R.hv[i] = bload(e.r_h, R.off[i]); R.zv[i] = bload(e.r_z, R.off[i]); }
   }
 }
 
@@ -252,7 +229,7 @@ __device__ __forceinline__ void epi_finish(const ConvParams& p, const EpiCtx& e,
     } else {
       o = (1.f - R.zv[i]) * R.hv[i] + R.zv[i] * tanhf(x);
     }
-    if (!e.skip_out) as_bstore(e.r_out, R.off[i], o);
+    if (!e.skip_out) bstore(e.r_out, R.off[i], o);
     ov[i] = o;
   }
   if (EPI != kEpiPartial && e.has_bs) {
@@ -263,10 +240,9 @@ __device__ __forceinline__ void epi_finish(const ConvParams& p, const EpiCtx& e,
       half4v hi, lo;
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float o = ov[m * 4 + k];
-        const _Float16 hk = (_Float16)o;
+        const _Float16 hk = split_hi(ov[m * 4 + k]);
         hi[k] = hk;
-        lo[k] = (_Float16)((o - (float)hk) * 2048.f);
+        lo[k] = split_lo(ov[m * 4 + k], hk);
       }
       amax = fmaxf(fmaxf(amax, fmaxf(fabsf(ov[m * 4]), fabsf(ov[m * 4 + 1]))), fmaxf(fabsf(ov[m * 4 + 2]), fabsf(ov[m * 4 + 3])));
       const unsigned blk = (unsigned)(col0 >> 3) + 2u * g + m;
@@ -324,7 +300,7 @@ __device__ __forceinline__ void epilogue_block(const ConvParams& p, const EpiCtx
     }
     if (g == 0) {
 #pragma unroll
-      for (int r = 0; r < 16; ++r) v[r] = acc_h[c][q][r] + acc_x[c][q][r] * (1.f / 2048.f);
+      for (int r = 0; r < 16; ++r) v[r] = join(acc_h[c][q][r], acc_x[c][q][r]);
     }
     epi_finish<EPI>(p, e, v, co_base + c * 32, half, g, bias_s, is_r, R[i % 3], amax, poff[q]);
   }
@@ -590,14 +566,8 @@ __global__ __launch_bounds__(256) void conv7x7_c1_kernel(const float* __restrict
 __device__ __forceinline__ void bs8_store(_Float16* __restrict__ out_bs, long long b, int c8tot, int blk, long long plane,
                                           long long pix, const float (&v)[8], float& amax) {
   half8 hi, lo;
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(v[j + 1])));
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const _Float16 hj = (_Float16)v[j];
-    hi[j] = hj;
-    lo[j] = (_Float16)((v[j] - (float)hj) * 2048.f);
-  }
+  amax = amax8(v, amax);
+  split_mode8(v, hi, lo);
   _Float16* rec = out_bs + ((b * 2 * c8tot + blk) * plane + pix) * 8;
   *reinterpret_cast<half8*>(rec) = hi;
   *reinterpret_cast<half8*>(rec + (long long)c8tot * plane * 8) = lo;
@@ -625,7 +595,7 @@ __global__ __launch_bounds__(256) void conv7x7_c1_tm_kernel(const float* __restr
   for (int idx = threadIdx.x; idx < 22 * 22; idx += 256) {
     const int py = idx / 22, px = idx - py * 22;
     const int gy = y0 - 3 + py, gx = x0 - 3 + px;
-    patch[idx] = as_bload(rs, (gy >= 0 && gy < H && gx >= 0 && gx < W) ? (unsigned)((gy * W + gx) * 4) : 0x7FFFFFF0u);
+    patch[idx] = bload(rs, (gy >= 0 && gy < H && gx >= 0 && gx < W) ? (unsigned)((gy * W + gx) * 4) : 0x7FFFFFF0u);
   }
   __syncthreads();
   const int ly = threadIdx.x >> 4, lx = threadIdx.x & 15;
@@ -665,9 +635,9 @@ __global__ __launch_bounds__(256) void conv7x7_c1_tm_kernel(const float* __restr
       if (copy_bs) {  // copy_out is a blocked split-fp16 tensor (ConvParams' BS8 comment): slot copy_coff % 8 of its block
         const int c8 = (copy_ctot + 7) >> 3;
         _Float16* rec = reinterpret_cast<_Float16*>(copy_out) + (((long long)b * 2 * c8 + (copy_coff >> 3)) * plane + (long long)gy * W + gx) * 8 + (copy_coff & 7);
-        const _Float16 hk = (_Float16)v;
+        const _Float16 hk = split_hi(v);
         rec[0] = hk;
-        rec[(long long)c8 * plane * 8] = (_Float16)((v - (float)hk) * 2048.f);
+        rec[(long long)c8 * plane * 8] = split_lo(v, hk);
         ovf_amax = fmaxf(ovf_amax, fabsf(v));
       } else {
         copy_out[((long long)b * copy_ctot + copy_coff) * plane + (long long)gy * W + gx] = v;
@@ -738,7 +708,7 @@ __global__ __launch_bounds__(256) void tap_shift_sum_kernel(const float* __restr
     for (int g = 0; g < 4; ++g)
 #pragma unroll
       for (int t = 0; t < 9; ++t)
-        v[g][t] = as_bload(rs, (toff[t] == 0x7FFFFFF0u || g0 + g >= groups) ? 0x7FFFFFF0u : toff[t] + (unsigned)(g0 + g) * gstep);
+        v[g][t] = bload(rs, (toff[t] == 0x7FFFFFF0u || g0 + g >= groups) ? 0x7FFFFFF0u : toff[t] + (unsigned)(g0 + g) * gstep);
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -804,7 +774,7 @@ __global__ __launch_bounds__(256) void pool2x_bs_kernel(const float* __restrict_
 #pragma unroll
   for (int j = 0; j < 8; ++j)
 #pragma unroll
-    for (int k = 0; k < 9; ++k) raw[j][k] = as_bload(rs, off[k] == 0x7FFFFFF0u ? off[k] : off[k] + (unsigned)j * pl4);
+    for (int k = 0; k < 9; ++k) raw[j][k] = bload(rs, off[k] == 0x7FFFFFF0u ? off[k] : off[k] + (unsigned)j * pl4);
   float v[8];
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
@@ -940,7 +910,6 @@ __global__ __launch_bounds__(256) void interp_bs_kernel(const float* __restrict_
 // Pipeline unit = one kernel row (KS taps) of a 16-channel chunk: weights double-buffered per unit,
 // the halo patch double-buffered per chunk; next unit/chunk is fetched into registers under the MFMAs.
 // ================================================================================================
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
 
 constexpr int kSplitKC = 16;
 // cache policy bits of the staged epilogue's result stores (buffer-store aux: 1 = sc0, 2 = nt, 16 = sc1).  0 = write-back: the
@@ -1173,9 +1142,9 @@ __global__ __launch_bounds__(LEAN ? 256 : 512, 2) void conv_split_kernel(ConvPar
   _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                      \
     const int col = (cg * ENB8 + (K)) * 8 + j;                                                        \
     const unsigned off = poff == 0x7FFFFFF0u ? poff : (unsigned)col * e.plane4 + poff;                 \
-    pav[K][j] = as_bload(e.r_add, off);                                                               \
-    if (EPI == AS_EPI_GRU_ZR || EPI == AS_EPI_LINEAR) phv[K][j] = as_bload(e.r_h, off);                \
-    if (EPI == AS_EPI_GRU_Q) { phv[K][j] = as_bload(e.r_h, off); pzv[K][j] = as_bload(e.r_z, off); }   \
+    pav[K][j] = bload(e.r_add, off);                                                               \
+    if (EPI == AS_EPI_GRU_ZR || EPI == AS_EPI_LINEAR) phv[K][j] = bload(e.r_h, off);                \
+    if (EPI == AS_EPI_GRU_Q) { phv[K][j] = bload(e.r_h, off); pzv[K][j] = bload(e.r_z, off); }   \
   }
 
 #define AS_SPLIT_LDOPS(TAP, S)                                                                          \
@@ -1407,16 +1376,15 @@ __global__ __launch_bounds__(LEAN ? 256 : 512, 2) void conv_split_kernel(ConvPar
       _Pragma("unroll") for (int i = 0; i < NPI; ++i) {                                                \
         const unsigned o0 = p_voff[i];                                                                \
         _Pragma("unroll") for (int j = 0; j < 8; ++j)                                                  \
-          v[i][j] = as_bload(rs, o0 == 0x7FFFFFF0u ? o0 : o0 + (unsigned)j * pl4);                     \
+          v[i][j] = bload(rs, o0 == 0x7FFFFFF0u ? o0 : o0 + (unsigned)j * pl4);                     \
       }                                                                                               \
       _Pragma("unroll") for (int i = 0; i < NPI; ++i) {                                                \
         _Pragma("unroll") for (int j = 0; j < 8; ++j) {                                                \
-          const _Float16 hj = (_Float16)v[i][j];                                                      \
+          const _Float16 hj = split_hi(v[i][j]);                                                      \
           c_hi[sc_][i][j] = hj;                                                                       \
-          c_lo[sc_][i][j] = (_Float16)((v[i][j] - (float)hj) * 2048.f);                                \
+          c_lo[sc_][i][j] = split_lo(v[i][j], hj);                                                    \
         }                                                                                             \
-        _Pragma("unroll") for (int j = 0; j < 8; j += 2)                                               \
-          ovf_amax = fmaxf(ovf_amax, fmaxf(fabsf(v[i][j]), fabsf(v[i][j + 1])));                       \
+        _Pragma("unroll") for (int j = 0; j < 8; j += 2) ovf_amax = amax2(ovf_amax, v[i][j], v[i][j + 1]); \
       }                                                                                               \
     }                                                                                                 \
   }
@@ -1609,7 +1577,7 @@ __global__ __launch_bounds__(LEAN ? 256 : 512, 2) void conv_split_kernel(ConvPar
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int col = c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            stage[col * BM + px_base + q * 32 + l31] = fmaxf(acc_h[c][q][r] + acc_x[c][q][r] * (1.f / 2048.f) + bias_s[col], 0.f);
+            stage[col * BM + px_base + q * 32 + l31] = fmaxf(join(acc_h[c][q][r], acc_x[c][q][r]) + bias_s[col], 0.f);
           }
     }
     __syncthreads();
@@ -1656,7 +1624,7 @@ __global__ __launch_bounds__(LEAN ? 256 : 512, 2) void conv_split_kernel(ConvPar
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const int col = co_base + c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-            stage[col * BM + px_base + q * 32 + l31] = acc_h[c][q][r] + acc_x[c][q][r] * (1.f / 2048.f);
+            stage[col * BM + px_base + q * 32 + l31] = join(acc_h[c][q][r], acc_x[c][q][r]);
           }
     }
     __syncthreads();
@@ -1691,12 +1659,12 @@ __global__ __launch_bounds__(LEAN ? 256 : 512, 2) void conv_split_kernel(ConvPar
         half8 hi, lo;
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
-          const _Float16 hj = (_Float16)ov[j];
+          const _Float16 hj = split_hi(ov[j]);
           hi[j] = hj;
-          lo[j] = (_Float16)((ov[j] - (float)hj) * 2048.f);
+          lo[j] = split_lo(ov[j], hj);
         }
 #pragma unroll
-        for (int j = 0; j < 8; j += 2) ovf_amax = fmaxf(ovf_amax, fmaxf(fabsf(ov[j]), fabsf(ov[j + 1])));
+        for (int j = 0; j < 8; j += 2) ovf_amax = amax2(ovf_amax, ov[j], ov[j + 1]);
         const unsigned off = poff == 0x7FFFFFF0u ? poff : (unsigned)(col0 >> 3) * (e.plane4 * 4u) + poff * 4u;
         if (col0 + 8 <= e.cvalid) {
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, hi), e.r_bs, (int)off, 0, AS_EPI_STORE_AUX);
@@ -1766,8 +1734,7 @@ __global__ void pack_weights_split_kernel(const float* __restrict__ w, _Float16*
   float v = 0.f;
   if (co < Cout && ci < Cin) v = transposed ? w[((long long)ci * Cout + co) * ntap + (ntap - 1 - tap)] : w[((long long)co * Cin + ci) * ntap + tap];
   as::fp16_saturate_mode();
-  const _Float16 hi = (_Float16)v;
-  wp[idx] = comp == 0 ? hi : (_Float16)((v - (float)hi) * 2048.f);
+  wp[idx] = split_part_mode(v, comp);
 }
 
 // ---- split-K finish: sum the K-slice slabs and apply the fused epilogue (one lane per output element) ----
@@ -1794,7 +1761,7 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(ConvParams p) {
     const unsigned o0 = (unsigned)((((long long)b * p.Cout_pad + co) * plane + pix) * 4), sl4 = (unsigned)(slab * 4);
     float part[8];
 #pragma unroll
-    for (int ks = 0; ks < 8; ++ks) part[ks] = as_bload(rws, ks < p.ksplit ? o0 + (unsigned)ks * sl4 : 0x7FFFFFF0u);
+    for (int ks = 0; ks < 8; ++ks) part[ks] = bload(rws, ks < p.ksplit ? o0 + (unsigned)ks * sl4 : 0x7FFFFFF0u);
     float x = 0.f;
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) x += part[ks];
@@ -1824,9 +1791,9 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(ConvParams p) {
   if (to_bs) {
     _Float16* rec = p.out_bs + (((long long)b * 2 * p.out_bs_c8tot + p.out_bs_coff8 + (cb_ >> 3)) * plane + pix) * 8 + (cb_ & 7);
     as::fp16_saturate_mode();
-    const _Float16 hk = (_Float16)o;
+    const _Float16 hk = split_hi(o);
     rec[0] = hk;
-    rec[(long long)p.out_bs_c8tot * plane * 8] = (_Float16)((o - (float)hk) * 2048.f);
+    rec[(long long)p.out_bs_c8tot * plane * 8] = split_lo(o, hk);
     as::note_split_overflow(fabsf(o), &g_split_overflow_conv);
   }
 }
@@ -2361,14 +2328,6 @@ int as_interp_bilinear_ac_bs(const float* x, void* out_bs, int B, int C, int H, 
   return as::check_launch("interp_bilinear_ac_bs");
 }
 
-unsigned as_conv_split_overflow(int reset) {
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_split_overflow_conv), sizeof(v)) != hipSuccess) return 0xFFFFFFFFu;
-  if (reset && v) {
-    const unsigned z = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_split_overflow_conv), &z, sizeof(z));
-  }
-  return v;
-}
+unsigned as_conv_split_overflow(int reset) { return as::read_reset_counter(&g_split_overflow_conv, reset); }
 
 }  // extern "C"

@@ -14,11 +14,11 @@
 // Weights arrive as MFMA A fragments (as_ir_block_pack_*: built once per weight version by the host wrapper, ops.IrBlockPack)
 // and are read from global memory (a chunk's fragments are shared by every block: L2-resident).
 #include "common.h"
+#include "split.h"
 
 namespace {
 
-using f32x16 = float __attribute__((ext_vector_type(16)));
-using half8 = _Float16 __attribute__((ext_vector_type(8)));
+using namespace as;  // split.h: vector types, split_hi / split_lo, join_fma, split_mfma_*
 
 struct IrParams {
   const float* x;       // [B, Cin, H, W]
@@ -104,9 +104,9 @@ __global__ __launch_bounds__(256) void ir_block_kernel(IrParams p) {
         const int idx = base + 256 * k;
         if (idx < total) {
           const int c = idx / G::NP, q = idx - c * G::NP;
-          const _Float16 h = (_Float16)v[k];
+          const _Float16 h = split_hi(v[k]);
           xs_hi[q * XP + c] = h;
-          xs_lo[q * XP + c] = (_Float16)((v[k] - (float)h) * 2048.f);
+          xs_lo[q * XP + c] = split_lo(v[k], h);
         }
       }
     }
@@ -158,9 +158,8 @@ __global__ __launch_bounds__(256) void ir_block_kernel(IrParams p) {
           if (ct < G::NCT) {
             const int off = (ct * 32 + l31) * XP + ks * 16 + 8 * half;
             const half8 bh = *reinterpret_cast<const half8*>(xs_hi + off), bl = *reinterpret_cast<const half8*>(xs_lo + off);
-            eh[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, eh[u], 0, 0, 0);
-            ex[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ex[u], 0, 0, 0);
-            ex[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, ex[u], 0, 0, 0);
+            eh[u] = split_mfma_h(eh[u], ah, bh);
+            ex[u] = split_mfma_x(ex[u], ah, al, bh, bl);
           }
         }
       }
@@ -171,7 +170,7 @@ __global__ __launch_bounds__(256) void ir_block_kernel(IrParams p) {
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int r = acc_row(i, half);
-            const float v = relu6f(fmaf(ex[u][i], 1.f / 2048.f, eh[u][i]) + b1s[ch * 32 + r]);
+            const float v = relu6f(join_fma(eh[u][i], ex[u][i]) + b1s[ch * 32 + r]);
             mid[r * G::MP + ct * 32 + l31] = col_in[u] ? v : 0.f;
           }
         }
@@ -215,9 +214,9 @@ __global__ __launch_bounds__(256) void ir_block_kernel(IrParams p) {
 #pragma unroll
           for (int kx = 0; kx < 3; ++kx) a = fmaf(wt[ky * 3 + kx], m0[ky * G::PW + kx], a);
         const float v = relu6f(a + bias);
-        const _Float16 h = (_Float16)v;
+        const _Float16 h = split_hi(v);
         dwo_hi[o * G::DP + c] = h;
-        dwo_lo[o * G::DP + c] = (_Float16)((v - (float)h) * 2048.f);
+        dwo_lo[o * G::DP + c] = split_lo(v, h);
       }
     }
     // the next chunk's expand fragments -> LDS (every wave finished this chunk's expand before the barrier above)
@@ -239,9 +238,8 @@ __global__ __launch_bounds__(256) void ir_block_kernel(IrParams p) {
             const half8 ah = w3h[u][ks], al = w3l[u][ks];
             const int off = (oc * 32 + l31) * G::DP + ks * 16 + 8 * half;
             const half8 bh = *reinterpret_cast<const half8*>(dwo_hi + off), bl = *reinterpret_cast<const half8*>(dwo_lo + off);
-            ph[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, ph[u], 0, 0, 0);
-            px[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, px[u], 0, 0, 0);
-            px[u] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, px[u], 0, 0, 0);
+            ph[u] = split_mfma_h(ph[u], ah, bh);
+            px[u] = split_mfma_x(px[u], ah, al, bh, bl);
           }
         }
       }
@@ -265,7 +263,7 @@ __global__ __launch_bounds__(256) void ir_block_kernel(IrParams p) {
         for (int i = 0; i < 16; ++i) {
           const int co = rt * 32 + acc_row(i, half);
           if (co < p.Cout) {
-            float v = fmaf(px[u][i], 1.f / 2048.f, ph[u][i]) + p.b3[co];
+            float v = join_fma(ph[u][i], px[u][i]) + p.b3[co];
             if (p.residual) v += xb[(long long)co * plane + (long long)oy * p.W + ox];
             ob[(long long)co * oplane + (long long)oy * p.Wo + ox] = v;
           }
@@ -294,10 +292,8 @@ __global__ __launch_bounds__(256) void ir_pack_frag_kernel(const float* __restri
     rt = (int)(blk / nks);
   }
   const int r = rt * 32 + (lane & 31), c = ks * 16 + 8 * (lane >> 5) + j;
-  float v = (r < rows && c < cols) ? w[(long long)r * ld + c] : 0.f;
-  v = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
-  const _Float16 h = (_Float16)v;
-  out[idx] = hl == 0 ? h : (_Float16)((v - (float)h) * 2048.f);
+  const float v = (r < rows && c < cols) ? w[(long long)r * ld + c] : 0.f;
+  out[idx] = split_part_clamp(v, hl);
 }
 
 }  // namespace

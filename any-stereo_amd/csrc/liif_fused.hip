@@ -22,30 +22,28 @@
 #include <algorithm>
 
 #include "common.h"
+#include "split.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
+using namespace as;  // split.h: vector types, join_fma / join, split_mfma_*, the pack kernels' split_part_clamp
 
 constexpr int kHid1 = 128, kHid2 = 64, kHid3 = 64, kOut = 9;
 constexpr int kFragBlocks = 64;                      // 1-KiB fragment blocks of the weight image (see liif_tail_pack_kernel)
 constexpr int kBiasFloats = kHid2 + kHid3 + 32;       // b2 | b3 | b4 (padded to 32 rows)
 constexpr int kImageBytes = kFragBlocks * 1024 + kBiasFloats * 4;
 constexpr int kBlkRel = 0, kBlkW2 = 8, kBlkW3 = 40, kBlkW4 = 56;
-constexpr float kF16Max = 65504.f;
 
+// The packed operand split of this file; NOT split.h's split_hi / split_lo: it rounds toward zero.
 // x = hi + lo/2048.  |x| >= 65504 (outside fp16) is clamped to +-65504 instead of becoming inf / NaN; the caller counts it.
 // `amax` tracks max |x| over everything a thread splits (one v_max3 per two elements): the kernel tests it once at its end.
 // v_cvt_pkrtz_f16_f32 converts two values per instruction; rounding toward zero never produces inf from a finite value, so
 // |x| >= 65504 saturates to +-65504 with no extra clamp (hi = rtz(x) leaves a residual < 1 ulp(fp16), lo = rtz(residual *
 // 2048): ~2^-20 relative per operand instead of round-to-nearest's 2^-22 — far inside this path's tolerance).
-using half2v = __attribute__((ext_vector_type(2))) _Float16;
-using u32x4v = __attribute__((ext_vector_type(4))) unsigned;
 __device__ __forceinline__ void split8(const float (&v)[8], half8& hi, half8& lo, float& amax) {
 #pragma unroll
   for (int j = 0; j < 8; j += 2) amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(v[j + 1])));
-  u32x4v ph, pl;
+  u32x4 ph, pl;
 #pragma unroll
   for (int j = 0; j < 8; j += 2) {
     const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(v[j], v[j + 1]));
@@ -62,7 +60,7 @@ __device__ __forceinline__ void split8(const float (&v)[8], half8& hi, half8& lo
 __device__ __forceinline__ void split8_pos(const float (&v)[8], half8& hi, half8& lo, int& imax) {
 #pragma unroll
   for (int j = 0; j < 8; j += 2) imax = max(max(imax, __builtin_bit_cast(int, v[j])), __builtin_bit_cast(int, v[j + 1]));
-  u32x4v ph, pl;
+  u32x4 ph, pl;
 #pragma unroll
   for (int j = 0; j < 8; j += 2) {
     const half2v h2 = __builtin_bit_cast(half2v, __builtin_amdgcn_cvt_pkrtz(v[j], v[j + 1]));
@@ -78,10 +76,6 @@ __device__ __forceinline__ void split8_pos(const float (&v)[8], half8& hi, half8
 __device__ __forceinline__ float relu_bits(float x) { return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0)); }
 
 __device__ unsigned g_split_overflow_liif;  // queries / pixels whose operands left the fp16 range (as_split_overflow_count)
-
-__device__ __forceinline__ void note_overflow(float amax) {  // amax >= 65504 (or NaN): some operand was saturated
-  if (__builtin_amdgcn_ballot_w64(!(amax < kF16Max)) != 0ull && (threadIdx.x & 63) == 0) atomicAdd(&g_split_overflow_liif, 1u);
-}
 
 // grid_sample(mode='nearest', align_corners=False) source index with ATen's fp32 operation sequence (no fma contraction)
 __device__ __forceinline__ int nearest_idx(float c, int n) {
@@ -295,9 +289,7 @@ __global__ __launch_bounds__(256) void liif_lowres_pack_kernel(LowresPackParams 
   const int c = lane & 31, half = lane >> 5;
   const int k = 16 * ks + 8 * half + j;
   const float v = k < p.K ? p.w[(long long)(32 * nt + c) * p.ldw + p.koff + k] : 0.f;
-  const float x = __builtin_amdgcn_fmed3f(v, -kF16Max, kF16Max);
-  const _Float16 hk = (_Float16)x;
-  p.img[idx] = hl == 0 ? hk : (_Float16)((x - (float)hk) * 2048.f);
+  p.img[idx] = split_part_clamp(v, hl);
 }
 
 struct F8 { float v[8]; };
@@ -387,18 +379,17 @@ __global__ __launch_bounds__(512) void liif_lowres_cl_kernel(LowresParams p) {
       half8 ah, al;
       split8(v, ah, al, amax);
       const half8 bh = W[((ks * 2 + ntl) * 2) * 64 + lane], bl = W[((ks * 2 + ntl) * 2 + 1) * 64 + lane];
-      acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc_h, 0, 0, 0);
-      acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc_x, 0, 0, 0);
-      acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc_x, 0, 0, 0);
+      acc_h = split_mfma_h(acc_h, ah, bh);
+      acc_x = split_mfma_x(acc_x, ah, al, bh, bl);
     }
     // C[row = pixel][col = output channel]: one register = 32 consecutive channels of one pixel (128 B per half wave)
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
       const long long opix = (long long)tile * 32 + acc_row(i, half);
-      if (opix < p.total) outp[opix * kHid1 + 32 * (nt0 + ntl) + c] = acc_h[i] + acc_x[i] * (1.f / 2048.f);
+      if (opix < p.total) outp[opix * kHid1 + 32 * (nt0 + ntl) + c] = join(acc_h[i], acc_x[i]);
     }
   }
-  note_overflow(amax);
+  note_split_overflow(amax, &g_split_overflow_liif);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -447,9 +438,7 @@ __global__ __launch_bounds__(256) void liif_tail_pack_kernel(PackParams p) {
       const int ks = t >> 1;
       v = r < kOut ? p.w4[r * kHid3 + perm_k(ks, half, j)] : 0.f;
     }
-    const float x = __builtin_amdgcn_fmed3f(v, -kF16Max, kF16Max);
-    const _Float16 hk = (_Float16)x;
-    p.image[idx] = hl == 0 ? hk : (_Float16)((x - (float)hk) * 2048.f);
+    p.image[idx] = split_part_clamp(v, hl);
   } else if (idx < kFragBlocks * 512 + kBiasFloats) {
     const int i = idx - kFragBlocks * 512;
     float* bias = reinterpret_cast<float*>(p.image + kFragBlocks * 512);
@@ -495,10 +484,9 @@ constexpr int kDirectCP = 48;                       // row pitch (floats) of a d
 constexpr int kDirectKS = kDirectCP / 16;
 constexpr int kImage1Bytes = kDirectKS * 8 * 1024;  // [ks][mt(4)][hi|lo][lane][8]
 
-#define AS_MFMA3(AH, AL, BH, BL, ACCH, ACCX)                               \
-  ACCH = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BH, ACCH, 0, 0, 0);    \
-  ACCX = __builtin_amdgcn_mfma_f32_32x32x16_f16(AH, BL, ACCX, 0, 0, 0);    \
-  ACCX = __builtin_amdgcn_mfma_f32_32x32x16_f16(AL, BH, ACCX, 0, 0, 0);
+#define AS_MFMA3(AH, AL, BH, BL, ACCH, ACCX) \
+  ACCH = split_mfma_h(ACCH, AH, BH);         \
+  ACCX = split_mfma_x(ACCX, AH, AL, BH, BL);
 
 // per-tile state that is prepared one tile ahead (coordinates, source rows, first gather group, disparity neighbours)
 struct TileCtx {
@@ -714,9 +702,8 @@ __global__ __launch_bounds__(DIRECT1 ? 512 : 256, DIRECT1 ? 1 : 2) void liif_tai
       f32x16 th, tx;
       {
         const half8 ah = W[(kBlkRel + 2 * t4) * 64 + lane], al = W[(kBlkRel + 2 * t4 + 1) * 64 + lane];
-        th = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, cur.xh, ga, 0, 0, 0);
-        tx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, cur.xl, zero16, 0, 0, 0);
-        tx = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, cur.xh, tx, 0, 0, 0);
+        th = split_mfma_h(ga, ah, cur.xh);
+        tx = split_mfma_x(zero16, ah, al, cur.xh, cur.xl);
         if constexpr (DIRECT1) {
 #pragma unroll
           for (int kd = 0; kd < kDirectKS; ++kd) {  // + W1[:, source-1 columns] . (its raw row): image1 [ks][mt][hi|lo][lane]
@@ -733,7 +720,7 @@ __global__ __launch_bounds__(DIRECT1 ? 512 : 256, DIRECT1 ? 1 : 2) void liif_tai
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j)
-          v[j] = relu_bits(DIRECT1 ? fmaf(tx[8 * s + j], 1.f / 2048.f, th[8 * s + j]) : fmaf(tx[8 * s + j], 1.f / 2048.f, th[8 * s + j]) + q8[j]);
+          v[j] = relu_bits(DIRECT1 ? join_fma(th[8 * s + j], tx[8 * s + j]) : join_fma(th[8 * s + j], tx[8 * s + j]) + q8[j]);
         __builtin_amdgcn_sched_barrier(0);
         if (t4 < 3 && NSRC > 1 && !DIRECT1) {  // this k-step's source-1 registers are free: fetch k-step ks + 2
 #pragma unroll
@@ -746,9 +733,8 @@ __global__ __launch_bounds__(DIRECT1 ? 512 : 256, DIRECT1 ? 1 : 2) void liif_tai
         for (int m = 0; m < 2; ++m) {
           const int blk = kBlkW2 + (ks * 2 + m) * 2;
           const half8 ah = W[blk * 64 + lane], al = W[(blk + 1) * 64 + lane];
-          a2h[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, a2h[m], 0, 0, 0);
-          a2x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ks == 0 ? zero16 : a2x[m], 0, 0, 0);
-          a2x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, a2x[m], 0, 0, 0);
+          a2h[m] = split_mfma_h(a2h[m], ah, bh);
+          a2x[m] = split_mfma_x(ks == 0 ? zero16 : a2x[m], ah, al, bh, bl);
         }
       }
       if (t4 < 3) ga = gn;
@@ -764,16 +750,15 @@ __global__ __launch_bounds__(DIRECT1 ? 512 : 256, DIRECT1 ? 1 : 2) void liif_tai
       const int mt = ks >> 1, s = ks & 1;
       float v[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = relu_bits(fmaf(a2x[mt][8 * s + j], 1.f / 2048.f, a2h[mt][8 * s + j]));
+      for (int j = 0; j < 8; ++j) v[j] = relu_bits(join_fma(a2h[mt][8 * s + j], a2x[mt][8 * s + j]));
       half8 bh, bl;
       split8_pos(v, bh, bl, imax);
 #pragma unroll
       for (int m = 0; m < 2; ++m) {
         const int blk = kBlkW3 + (ks * 2 + m) * 2;
         const half8 ah = W[blk * 64 + lane], al = W[(blk + 1) * 64 + lane];
-        a3h[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, a3h[m], 0, 0, 0);
-        a3x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ks == 0 ? zero16 : a3x[m], 0, 0, 0);
-        a3x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, a3x[m], 0, 0, 0);
+        a3h[m] = split_mfma_h(a3h[m], ah, bh);
+        a3x[m] = split_mfma_x(ks == 0 ? zero16 : a3x[m], ah, al, bh, bl);
       }
     }
     // layer 4: 64 -> 9 (rows 9..31 of the tile carry zero weights)
@@ -785,19 +770,18 @@ __global__ __launch_bounds__(DIRECT1 ? 512 : 256, DIRECT1 ? 1 : 2) void liif_tai
       const int mt = ks >> 1, s = ks & 1;
       float v[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = relu_bits(fmaf(a3x[mt][8 * s + j], 1.f / 2048.f, a3h[mt][8 * s + j]));
+      for (int j = 0; j < 8; ++j) v[j] = relu_bits(join_fma(a3h[mt][8 * s + j], a3x[mt][8 * s + j]));
       half8 bh, bl;
       split8_pos(v, bh, bl, imax);
       const int blk = kBlkW4 + ks * 2;
       const half8 ah = W[blk * 64 + lane], al = W[(blk + 1) * 64 + lane];
-      a4h = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, a4h, 0, 0, 0);
-      a4x = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ks == 0 ? zero16 : a4x, 0, 0, 0);
-      a4x = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, a4x, 0, 0, 0);
+      a4h = split_mfma_h(a4h, ah, bh);
+      a4x = split_mfma_x(ks == 0 ? zero16 : a4x, ah, al, bh, bl);
     }
     // logits: half 0 holds rows 0..3 (registers 0..3) and row 8 (register 4), half 1 rows 4..7 (registers 0..3)
     float lg[5];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) lg[i] = a4h[i] + a4x[i] * (1.f / 2048.f);
+    for (int i = 0; i < 5; ++i) lg[i] = join(a4h[i], a4x[i]);
     if (logitsp && cur.valid) {
       const int b = (int)(cur.t / p.Q);
       const int q = (int)(cur.t - (long long)b * p.Q);
@@ -820,7 +804,7 @@ __global__ __launch_bounds__(DIRECT1 ? 512 : 256, DIRECT1 ? 1 : 2) void liif_tai
     dsum += __shfl_xor(dsum, 32);
     if (outp && cur.valid && !half) outp[cur.t] = dsum / ssum;
   }
-  note_overflow(fmaxf(amax, __builtin_bit_cast(float, imax)));
+  note_split_overflow(fmaxf(amax, __builtin_bit_cast(float, imax)), &g_split_overflow_liif);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
@@ -867,9 +851,7 @@ __global__ __launch_bounds__(256) void liif_mlp_bwd_pack_kernel(PackTParams p) {
     const int m = (t >> 1) & 3, ks = t >> 3;
     v = p.w2[perm_k(ks, half, j) * kHid1 + 32 * m + r];
   }
-  const float x = __builtin_amdgcn_fmed3f(v, -kF16Max, kF16Max);
-  const _Float16 hk = (_Float16)x;
-  p.image[idx] = hl == 0 ? hk : (_Float16)((x - (float)hk) * 2048.f);
+  p.image[idx] = split_part_clamp(v, hl);
 }
 
 struct MlpBwdParams {
@@ -1028,9 +1010,8 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
       f32x16 th, tx;
       {
         const half8 ah = W[(kBlkRel + 2 * t4) * 64 + lane], al = W[(kBlkRel + 2 * t4 + 1) * 64 + lane];
-        th = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, cur.xh, ga, 0, 0, 0);
-        tx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, cur.xl, zero16, 0, 0, 0);
-        tx = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, cur.xh, tx, 0, 0, 0);
+        th = split_mfma_h(ga, ah, cur.xh);
+        tx = split_mfma_x(zero16, ah, al, cur.xh, cur.xl);
       }
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
@@ -1039,7 +1020,7 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
         const float q8[8] = {qa.x, qa.y, qa.z, qa.w, qb.x, qb.y, qb.z, qb.w};
         float v[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = relu_bits(fmaf(tx[8 * s + j], 1.f / 2048.f, th[8 * s + j]) + q8[j]);
+        for (int j = 0; j < 8; ++j) v[j] = relu_bits(join_fma(th[8 * s + j], tx[8 * s + j]) + q8[j]);
         __builtin_amdgcn_sched_barrier(0);
         if (t4 < 3) {
 #pragma unroll
@@ -1057,9 +1038,8 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
         for (int m = 0; m < 2; ++m) {
           const int blk = kBlkW2 + (ks * 2 + m) * 2;
           const half8 ah = W[blk * 64 + lane], al = W[(blk + 1) * 64 + lane];
-          a2h[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, a2h[m], 0, 0, 0);
-          a2x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ks == 0 ? zero16 : a2x[m], 0, 0, 0);
-          a2x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, a2x[m], 0, 0, 0);
+          a2h[m] = split_mfma_h(a2h[m], ah, bh);
+          a2x[m] = split_mfma_x(ks == 0 ? zero16 : a2x[m], ah, al, bh, bl);
         }
       }
       if (t4 < 3) ga = gn;
@@ -1074,7 +1054,7 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
       const int mt = ks >> 1, s = ks & 1;
       float v[8];
 #pragma unroll
-      for (int j = 0; j < 8; ++j) v[j] = relu_bits(fmaf(a2x[mt][8 * s + j], 1.f / 2048.f, a2h[mt][8 * s + j]));
+      for (int j = 0; j < 8; ++j) v[j] = relu_bits(join_fma(a2h[mt][8 * s + j], a2x[mt][8 * s + j]));
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         m2[mt] |= (v[j] > 0.f ? 1u : 0u) << (8 * s + j);
@@ -1086,16 +1066,15 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
       for (int m = 0; m < 2; ++m) {
         const int blk = kBlkW3 + (ks * 2 + m) * 2;
         const half8 ah = W[blk * 64 + lane], al = W[(blk + 1) * 64 + lane];
-        a3h[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, a3h[m], 0, 0, 0);
-        a3x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, ks == 0 ? zero16 : a3x[m], 0, 0, 0);
-        a3x[m] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, a3x[m], 0, 0, 0);
+        a3h[m] = split_mfma_h(a3h[m], ah, bh);
+        a3x[m] = split_mfma_x(ks == 0 ? zero16 : a3x[m], ah, al, bh, bl);
       }
     }
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
       for (int i = 0; i < 16; ++i) {
-        const float v = relu_bits(fmaf(a3x[mt][i], 1.f / 2048.f, a3h[mt][i]));
+        const float v = relu_bits(join_fma(a3h[mt][i], a3x[mt][i]));
         m3[mt] |= (v > 0.f ? 1u : 0u) << i;
         AS_BWD_HD_STORE(__builtin_bit_cast(unsigned, v), r_h3, (int)vo64, (int)((32 * mt + AS_ROW(i)) * q4), 0);
       }
@@ -1117,16 +1096,15 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
 #pragma unroll
     for (int m = 0; m < 2; ++m) {
       const half8 ah = WT[(kTBlk4 + 2 * m) * 64 + lane], al = WT[(kTBlk4 + 2 * m + 1) * 64 + lane];
-      f32x16 gh = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, zero16, 0, 0, 0);
-      f32x16 gx = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, zero16, 0, 0, 0);
-      gx = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, gx, 0, 0, 0);
+      f32x16 gh = split_mfma_h(zero16, ah, bh);
+      f32x16 gx = split_mfma_x(zero16, ah, al, bh, bl);
 #pragma unroll
       for (int s = 0; s < 2; ++s) {
         float v[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int i = 8 * s + j;
-          v[j] = ((m3[m] >> i) & 1u) ? fmaf(gx[i], 1.f / 2048.f, gh[i]) : 0.f;
+          v[j] = ((m3[m] >> i) & 1u) ? join_fma(gh[i], gx[i]) : 0.f;
           AS_BWD_HD_STORE(__builtin_bit_cast(unsigned, v[j]), r_d3, (int)vo64, (int)((32 * m + AS_ROW(i)) * q4), 0);
         }
         split8(v, f3h[2 * m + s], f3l[2 * m + s], amax);
@@ -1149,7 +1127,7 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
 #pragma unroll
         for (int j = 0; j < 8; ++j) {
           const int i = 8 * s + j;
-          v[j] = ((m2[m] >> i) & 1u) ? fmaf(gx[i], 1.f / 2048.f, gh[i]) : 0.f;
+          v[j] = ((m2[m] >> i) & 1u) ? join_fma(gh[i], gx[i]) : 0.f;
           AS_BWD_HD_STORE(__builtin_bit_cast(unsigned, v[j]), r_d2, (int)vo64, (int)((32 * m + AS_ROW(i)) * q4), 0);
         }
         split8(v, f2h[2 * m + s], f2l[2 * m + s], amax);
@@ -1168,14 +1146,14 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
       if constexpr (!fuse1) {
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const float v = ((m1[m] >> i) & 1u) ? fmaf(gx[i], 1.f / 2048.f, gh[i]) : 0.f;
+          const float v = ((m1[m] >> i) & 1u) ? join_fma(gh[i], gx[i]) : 0.f;
           AS_BWD_HD_STORE(__builtin_bit_cast(unsigned, v), r_d1, (int)vo128, (int)((32 * m + AS_ROW(i)) * q4), 0);
         }
       } else {
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the previous m-tile's column reads are done before the tile is overwritten
 #pragma unroll
         for (int i = 0; i < 16; ++i) {
-          const float v = (cur.valid && ((m1[m] >> i) & 1u)) ? fmaf(gx[i], 1.f / 2048.f, gh[i]) : 0.f;
+          const float v = (cur.valid && ((m1[m] >> i) & 1u)) ? join_fma(gh[i], gx[i]) : 0.f;
           stage[(AS_ROW(i) + 4 * half) * kStageRow + c] = v;  // [channel row of the m-tile][query]
           float s0 = v, s1 = v;
 #pragma unroll
@@ -1213,7 +1191,7 @@ __global__ __launch_bounds__(512) void liif_mlp_bwd_kernel(MlpBwdParams P) {
         if (half == 0) atomicAdd(P.dwrel + (32 * m + c) * 4 + k, tot);
       }
   }
-  note_overflow(fmaxf(amax, __builtin_bit_cast(float, imax)));
+  note_split_overflow(fmaxf(amax, __builtin_bit_cast(float, imax)), &g_split_overflow_liif);
 }
 
 // channels-last copy of a (<= 48-channel) structure feature: out[b][p][0..kDirectCP) = cat(srcs)[b, :, p], zero padded — the rows the
@@ -1551,14 +1529,6 @@ int as_liif_mlp_bwd(const float* u0, const float* u1, const float* coord, const 
   return as::check_launch("liif_mlp_bwd");
 }
 
-unsigned as_liif_split_overflow(int reset) {
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_split_overflow_liif), sizeof(v)) != hipSuccess) return 0xFFFFFFFFu;
-  if (reset && v) {
-    const unsigned z = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_split_overflow_liif), &z, sizeof(z));
-  }
-  return v;
-}
+unsigned as_liif_split_overflow(int reset) { return as::read_reset_counter(&g_split_overflow_liif, reset); }
 
 }  // extern "C"

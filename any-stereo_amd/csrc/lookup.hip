@@ -8,8 +8,11 @@
 // once (one float4 per tap covers 4 geo channels in the [B,H,W,D,G] layout) and reused by
 // all 2r+1 interpolated taps: compulsory traffic only, no zero-init pass on the output.
 #include "common.h"
+#include "split.h"
 
 namespace {
+
+using namespace as;  // split.h: vector types, operand split / join, split_mfma
 
 struct LookupParams {
   const float* geo[AS_MAX_LEVELS];
@@ -26,8 +29,6 @@ struct LookupParams {
   int geo_bytes[AS_MAX_LEVELS];
   int corr_bytes[AS_MAX_LEVELS];
 };
-
-using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 // position of tap k (kk = k - R) given the level-scaled base; returns window slot selection.
 //   xk = xbase + kk (one fp32 add, as the reference's `dx + disp/2**i`, geometry.py:43,52)
@@ -366,11 +367,6 @@ __global__ __launch_bounds__(256) void lookup_fwd_quad_kernel(LookupParams p) {
 // split-fp16 link tensor (conv.hip, `out_bs`) — what the next convolution's loaders stage by LDS-DMA — and / or as fp32 NCHW.
 // Wave w: output channels [32 (w&1), +32) x pixels [32 (w>>1), +32); its 22 weight fragments (16 B per lane, packed by
 // frag_pack_kernel) are fetched at kernel entry, so they are in flight during the gather.
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using half4v = __attribute__((ext_vector_type(4))) _Float16;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-
 struct FusedParams {
   const _Float16* wimg;  // [ks][mt(2)][hi|lo][lane][8]
   const float* bias;     // [64] or null
@@ -418,18 +414,16 @@ __device__ __forceinline__ void lookup_convc1_body(const LookupParams& p, const 
 #pragma unroll
     for (int j = 0; j < 8; ++j) v[j] = tp[(16 * ks + j) * TS];
     half8 bh, bl;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(v[j + 1])));
+    amax = amax8(v, amax);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const float x = __builtin_amdgcn_fmed3f(v[j], -65504.f, 65504.f);
-      const _Float16 hk = (_Float16)x;
+      const float x = clamp_f16(v[j]);
+      const _Float16 hk = split_hi(x);
       bh[j] = hk;
-      bl[j] = (_Float16)((x - (float)hk) * 2048.f);
+      bl[j] = split_lo(x, hk);
     }
-    acc_h = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bh, acc_h, 0, 0, 0);
-    acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[ks], bl, acc_x, 0, 0, 0);
-    acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[ks], bh, acc_x, 0, 0, 0);
+    acc_h = split_mfma_h(acc_h, ah[ks], bh);
+    acc_x = split_mfma_x(acc_x, ah[ks], al[ks], bh, bl);
   }
   const long long pix = (long long)bid * PX + 32 * nt + c;
   if (pix < p.P) {
@@ -440,7 +434,7 @@ __device__ __forceinline__ void lookup_convc1_body(const LookupParams& p, const 
       float o[4];
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float x = acc_h[4 * qd + k] + acc_x[4 * qd + k] * (1.f / 2048.f);
+        const float x = join(acc_h[4 * qd + k], acc_x[4 * qd + k]);
         o[k] = f.relu ? fmaxf(x, 0.f) : x;
       }
       const int ch = 32 * mt + 8 * qd + 4 * half;  // this lane's four channels of block (4 mt + qd)
@@ -454,10 +448,10 @@ __device__ __forceinline__ void lookup_convc1_body(const LookupParams& p, const 
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           amax = fmaxf(amax, fabsf(o[k]));
-          const float x = __builtin_amdgcn_fmed3f(o[k], -65504.f, 65504.f);
-          const _Float16 hk = (_Float16)x;
+          const float xc = clamp_f16(o[k]);
+          const _Float16 hk = split_hi(xc);
           hi[k] = hk;
-          lo[k] = (_Float16)((x - (float)hk) * 2048.f);
+          lo[k] = split_lo(xc, hk);
         }
         const long long blk = f.cb_off + 4 * mt + qd;
         const long long e_hi = ((((long long)b * 2 + 0) * f.cb_tot + blk) * p.HW + rem) * 8 + 4 * half;
@@ -467,7 +461,7 @@ __device__ __forceinline__ void lookup_convc1_body(const LookupParams& p, const 
       }
     }
   }
-  if (__builtin_amdgcn_ballot_w64(!(amax < 65504.f)) != 0ull && lane == 0) atomicAdd(&g_split_overflow_lookup, 1u);
+  note_split_overflow(amax, &g_split_overflow_lookup);
 }
 
 
@@ -503,9 +497,7 @@ __global__ __launch_bounds__(256) void frag_pack_direct_kernel(const float* w, _
   else if (ks == 9) chan = h * 81 + 72 + j;
   else if (j == 0) chan = h * 81 + 72 + 8;
   const float v = chan >= 0 ? w[(long long)co * 162 + chan] : 0.f;
-  const float x = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
-  const _Float16 hk = (_Float16)x;
-  img[idx] = hl == 0 ? hk : (_Float16)((x - (float)hk) * 2048.f);
+  img[idx] = split_part_clamp(v, hl);
 }
 
 typedef __attribute__((address_space(3))) void lk_lds_void;
@@ -639,21 +631,19 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void lookup_convc1_direct_kernel(Loo
       }
     }
     half8 bh, bl;
-#pragma unroll
-    for (int j = 0; j < 8; j += 2) amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(v[j + 1])));
+    amax = amax8(v, amax);
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
-      const _Float16 hk = (_Float16)v[j];  // MODE.FP16_OVFL: |v| >= 65504 saturates (counted below), never inf / NaN
+      const _Float16 hk = split_hi(v[j]);  // MODE.FP16_OVFL: |v| >= 65504 saturates (counted below), never inf / NaN
       bh[j] = hk;
-      bl[j] = (_Float16)((v[j] - (float)hk) * 2048.f);
+      bl[j] = split_lo(v[j], hk);
     }
 #pragma unroll
     for (int t = 0; t < 2; ++t) {
       const half8 ah = wfr[((ks * 2 + t) * 2 + 0) * 64];
       const half8 al = wfr[((ks * 2 + t) * 2 + 1) * 64];
-      acc_h[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc_h[t], 0, 0, 0);
-      acc_x[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc_x[t], 0, 0, 0);
-      acc_x[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc_x[t], 0, 0, 0);
+      acc_h[t] = split_mfma_h(acc_h[t], ah, bh);
+      acc_x[t] = split_mfma_x(acc_x[t], ah, al, bh, bl);
     }
   }
 #endif
@@ -667,7 +657,7 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void lookup_convc1_direct_kernel(Loo
         float o[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          const float xo = acc_h[t][4 * qd + k] + acc_x[t][4 * qd + k] * (1.f / 2048.f);
+          const float xo = join(acc_h[t][4 * qd + k], acc_x[t][4 * qd + k]);
           o[k] = f.relu ? fmaxf(xo, 0.f) : xo;
         }
         const int ch = 32 * t + 8 * qd + 4 * h;  // this lane's four channels of block (4 t + qd)
@@ -681,9 +671,9 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void lookup_convc1_direct_kernel(Loo
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             amax = fmaxf(amax, fabsf(o[k]));
-            const _Float16 hk = (_Float16)o[k];
+            const _Float16 hk = split_hi(o[k]);
             hi[k] = hk;
-            lo[k] = (_Float16)((o[k] - (float)hk) * 2048.f);
+            lo[k] = split_lo(o[k], hk);
           }
           const long long blk = f.cb_off + 4 * t + qd;
           const long long e_hi = ((((long long)b * 2 + 0) * f.cb_tot + blk) * p.HW + rem) * 8 + 4 * h;
@@ -693,7 +683,7 @@ __global__ __launch_bounds__(NWAVE * 64, 2) void lookup_convc1_direct_kernel(Loo
         }
       }
   }
-  if (__builtin_amdgcn_ballot_w64(!(amax < 65504.f)) != 0ull && lane == 0) atomicAdd(&g_split_overflow_lookup, 1u);
+  note_split_overflow(amax, &g_split_overflow_lookup);
 }
 
 // ---- the front of a GRU iteration in ONE launch -------------------------------------------------------------------------------
@@ -821,10 +811,10 @@ __global__ __launch_bounds__(256, 2) void loop_front_kernel(LookupParams p, Fuse
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float v = fmaxf(acc[j] + (b7 ? b7[c0 + 8 * k + j] : 0.f), 0.f);
-        amax = fmaxf(amax, v);
-        const _Float16 hj = (_Float16)v;
-        hi[j] = hj;
-        lo[j] = (_Float16)((v - (float)hj) * 2048.f);
+        amax = fmaxf(amax, v);  // a ReLU output: no fabsf
+        const _Float16 hk = split_hi(v);
+        hi[j] = hk;
+        lo[j] = split_lo(v, hk);
       }
       _Float16* rec = q.d1_bs + (((long long)b * 2 * 8 + (c0 >> 3) + k) * plane + pixo) * 8;
       *reinterpret_cast<half8*>(rec) = hi;
@@ -836,9 +826,9 @@ __global__ __launch_bounds__(256, 2) void loop_front_kernel(LookupParams p, Fuse
       const float v = patch[(ly + 3) * 22 + lx + 3];
       const int c8 = (q.copy_ctot + 7) >> 3;
       _Float16* rec = q.copy_bs + (((long long)b * 2 * c8 + (q.copy_coff >> 3)) * plane + pixo) * 8 + (q.copy_coff & 7);
-      const _Float16 hk = (_Float16)v;
+      const _Float16 hk = split_hi(v);
       rec[0] = hk;
-      rec[(long long)c8 * plane * 8] = (_Float16)((v - (float)hk) * 2048.f);
+      rec[(long long)c8 * plane * 8] = split_lo(v, hk);
       amax = fmaxf(amax, fabsf(v));
     }
   }
@@ -855,9 +845,7 @@ __global__ __launch_bounds__(256) void frag_pack_kernel(const float* w, int cout
   const int hl = blk & 1, t = (blk >> 1) % tiles, ks = (blk >> 1) / tiles;
   const int k = 16 * ks + 8 * (lane >> 5) + j;
   const float v = k < K ? w[(long long)(32 * t + (lane & 31)) * ldw + koff + k] : 0.f;
-  const float x = __builtin_amdgcn_fmed3f(v, -65504.f, 65504.f);
-  const _Float16 hk = (_Float16)x;
-  img[idx] = hl == 0 ? hk : (_Float16)((x - (float)hk) * 2048.f);
+  img[idx] = split_part_clamp(v, hl);
 }
 
 // Backward w.r.t. the volumes: the transpose of the above.  Each (pixel, task) owns a private
@@ -1248,14 +1236,6 @@ int as_loop_front_fwd(const float* const* geo, const float* const* corr, const f
   return as::check_launch("loop_front_fwd");
 }
 
-unsigned as_lookup_split_overflow(int reset) {
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_split_overflow_lookup), sizeof(v)) != hipSuccess) return 0xFFFFFFFFu;
-  if (reset && v) {
-    const unsigned z = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_split_overflow_lookup), &z, sizeof(z));
-  }
-  return v;
-}
+unsigned as_lookup_split_overflow(int reset) { return as::read_reset_counter(&g_split_overflow_lookup, reset); }
 
 }  // extern "C"

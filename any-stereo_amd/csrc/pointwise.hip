@@ -26,14 +26,11 @@
 // OPS: the layer has an `add` tensor or a residual (pw_epilogue).  No block waits on another; the grid is a function of the shape.
 #include "common.h"
 #include "conv_plan.h"
+#include "split.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
-using f32x2 = __attribute__((ext_vector_type(2))) float;
-using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
+using namespace as;  // split.h: the arithmetic conv_split_kernel compiles too, which is why the two agree bit for bit
 
 constexpr int kPwRun = 64;          // pixels per wave
 constexpr int kPwWaves = 2;         // waves per block of the KSWEEP kernels
@@ -67,22 +64,6 @@ struct PwParams {
 
 __device__ unsigned g_split_overflow_pw;  // as_pointwise_split_overflow
 
-// conv.hip's act_apply, expression for expression
-__device__ __forceinline__ float act_apply(float v, int act) {
-  switch (act) {
-    case AS_ACT_RELU: return fmaxf(v, 0.f);
-    case AS_ACT_SIGMOID: return 1.f / (1.f + expf(-v));
-    case AS_ACT_TANH: return tanhf(v);
-    case AS_ACT_RELU6: return fminf(fmaxf(v, 0.f), 6.f);
-    case AS_ACT_LEAKY: return v >= 0.f ? v : 0.01f * v;
-    default: return v;
-  }
-}
-
-__device__ __forceinline__ float pw_bload(__amdgpu_buffer_rsrc_t r, unsigned off) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)off, 0, 0));
-}
-
 // The two pixels of a lane in one channel plane.  o0 / o1: byte offsets of the pixels inside the descriptor's window, or kOOB.
 template <bool VEC>
 __device__ __forceinline__ void pw_load2(__amdgpu_buffer_rsrc_t r, unsigned o0, unsigned o1, float& a, float& b) {
@@ -91,8 +72,8 @@ __device__ __forceinline__ void pw_load2(__amdgpu_buffer_rsrc_t r, unsigned o0, 
     a = v[0];
     b = v[1];
   } else {
-    a = pw_bload(r, o0);
-    b = pw_bload(r, o1);
+    a = bload(r, o0);
+    b = bload(r, o1);
   }
 }
 
@@ -115,18 +96,6 @@ __device__ __forceinline__ void pw_load_chunk(const PwParams& p, int b, int k, i
   const unsigned b0 = p0 + (unsigned)(8 * hf) * pl4, b1 = p1 + (unsigned)(8 * hf) * pl4;
 #pragma unroll
   for (int j = 0; j < 8; ++j) pw_load2<VEC>(rs, b0 + (unsigned)j * pl4, b1 + (unsigned)j * pl4, v[0][j], v[1][j]);
-}
-
-// the operand split of conv_split_kernel's loaders
-__device__ __forceinline__ void pw_split(const float (&v)[8], half8& hi, half8& lo, float& amax) {
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const _Float16 hj = (_Float16)v[j];
-    hi[j] = hj;
-    lo[j] = (_Float16)((v[j] - (float)hj) * 2048.f);
-  }
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(v[j + 1])));
 }
 
 // A fragments of (chunk k, output tile ct): rows ct * 32 + r of the hi and of the lo image; chunks past the pack read 0
@@ -173,7 +142,7 @@ __device__ __forceinline__ PwEpi pw_make_epi(const PwParams& p, int b) {
 __device__ __forceinline__ void pw_load_bias(const PwEpi& e, int ct, int hf, float (&bs)[16]) {
   const unsigned bb = (unsigned)(ct * 32 + 4 * hf) * 4u;
 #pragma unroll
-  for (int row = 0; row < 16; ++row) bs[row] = pw_bload(e.r_bias, bb + (unsigned)((row & 3) + 8 * (row >> 2)) * 4u);
+  for (int row = 0; row < 16; ++row) bs[row] = bload(e.r_bias, bb + (unsigned)((row & 3) + 8 * (row >> 2)) * 4u);
 }
 
 // epi_finish<AS_EPI_LINEAR> of conv.hip on output tile ct: the lane's 16 channels x 2 pixels.
@@ -203,8 +172,8 @@ __device__ __forceinline__ void pw_epilogue(const PwParams& p, const PwEpi& e, i
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       const int row = g * 4 + i;
-      const float v0 = ah[0][row] + ax[0][row] * (1.f / 2048.f);
-      const float v1 = ah[1][row] + ax[1][row] * (1.f / 2048.f);
+      const float v0 = join(ah[0][row], ax[0][row]);
+      const float v1 = join(ah[1][row], ax[1][row]);
       x[0][i] = v0 + bs[row] + av[0][row];
       x[1][i] = v1 + bs[row] + av[1][row];
     }
@@ -290,8 +259,10 @@ __device__ __forceinline__ void pw_resident(const PwParams& p, unsigned char* ld
   }
 #pragma unroll
   for (int k = 0; k < NCH; ++k) {
-    pw_split(v[k][0], bh[k][0], bl[k][0], amax);
-    pw_split(v[k][1], bh[k][1], bl[k][1], amax);
+    split_mode8(v[k][0], bh[k][0], bl[k][0]);
+    amax = amax8(v[k][0], amax);
+    split_mode8(v[k][1], bh[k][1], bl[k][1]);
+    amax = amax8(v[k][1], amax);
   }
   __syncthreads();
   if (idle) return;
@@ -363,8 +334,10 @@ __device__ __forceinline__ void pw_ksweep(const PwParams& p) {
 #pragma unroll
     for (int g = 0; g < G; ++g) {
       half8 bh[2], bl[2];
-      pw_split(cur[g][0], bh[0], bl[0], amax);
-      pw_split(cur[g][1], bh[1], bl[1], amax);
+      split_mode8(cur[g][0], bh[0], bl[0]);
+      amax = amax8(cur[g][0], amax);
+      split_mode8(cur[g][1], bh[1], bl[1]);
+      amax = amax8(cur[g][1], amax);
 #pragma unroll
       for (int t = 0; t < NT; ++t) {
         PW_CHUNK(ah[t], ax[t], a_hi[t][g], a_lo[t][g], bh, bl)
@@ -513,14 +486,6 @@ int as_conv1x1_stream(const as_conv_desc* d, void* stream) {
 #undef PW_GO
 }
 
-unsigned as_pointwise_split_overflow(int reset) {
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_split_overflow_pw), sizeof(v)) != hipSuccess) return 0xFFFFFFFFu;
-  if (reset && v) {
-    const unsigned z = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_split_overflow_pw), &z, sizeof(z));
-  }
-  return v;
-}
+unsigned as_pointwise_split_overflow(int reset) { return as::read_reset_counter(&g_split_overflow_pw, reset); }
 
 }  // extern "C"

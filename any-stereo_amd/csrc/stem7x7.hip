@@ -8,11 +8,11 @@
 // like conv.hip) and every operand fetch is one aligned, conflict-free ds_read_b128.  The whole weight set (45 KB of fragments)
 // stays in LDS; blocks are persistent over 8 x 16 pixel tiles, two blocks per CU.
 #include "common.h"
+#include "split.h"
 
 namespace {
 
-using half8 = _Float16 __attribute__((ext_vector_type(8)));
-using f32x16 = float __attribute__((ext_vector_type(16)));
+using namespace as;  // split.h: vector types, split_hi / split_lo, join, split_mfma_*, act_apply
 
 constexpr int kTH = 8, kTW = 16;                 // pixel tile
 constexpr int kPH = kTH + 6, kPWraw = kTW + 6;   // halo patch rows / raw columns
@@ -30,14 +30,6 @@ struct StemParams {
   int B, H, W, tiles_x, tiles_y, act;
 };
 
-__device__ __forceinline__ float act_apply(float v, int act) {
-  switch (act) {
-    case AS_ACT_RELU: return fmaxf(v, 0.f);
-    case AS_ACT_LEAKY: return v >= 0.f ? v : 0.01f * v;
-    default: return v;
-  }
-}
-
 // fragments of W [64][3][7][7] (row-major fp32): k = row*8 + kx, row = ci*7 + ky; A operand of lane (co, k-half) = 8 k values
 __global__ __launch_bounds__(256) void stem_pack_kernel(const float* __restrict__ w, _Float16* __restrict__ pack) {
   const int t = blockIdx.x * 256 + threadIdx.x;  // (step, half, co, j)
@@ -46,8 +38,8 @@ __global__ __launch_bounds__(256) void stem_pack_kernel(const float* __restrict_
   const int row = 2 * step + half;
   float v = 0.f;
   if (row < 21 && j < 7) v = w[(co * 3 + row / 7) * 49 + (row % 7) * 7 + j];
-  const _Float16 hi = (_Float16)v;
-  const _Float16 lo = (_Float16)((v - (float)hi) * 2048.f);
+  const _Float16 hi = split_hi(v);
+  const _Float16 lo = split_lo(v, hi);
   pack[(((step * 2 + 0) * 2 + half) * 64 + co) * 8 + j] = hi;
   pack[(((step * 2 + 1) * 2 + half) * 64 + co) * 8 + j] = lo;
 }
@@ -66,6 +58,8 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(StemParams p) {
   const int py = 2 * wave + (l31 >> 4), px = l31 & 15;
   const long long plane = (long long)p.H * p.W;
   const int ntile = p.B * p.tiles_y * p.tiles_x;
+  // as_conv7x7_c3 admits NONE / RELU / LEAKY only: said here, the shared act_apply compiles to the two cases this kernel needs
+  const int act = p.act == AS_ACT_RELU ? AS_ACT_RELU : p.act == AS_ACT_LEAKY ? AS_ACT_LEAKY : AS_ACT_NONE;
   // the lane's 32 output channels' bias, once per (persistent) block
   float bias_r[2][16];
 #pragma unroll
@@ -110,9 +104,9 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(StemParams p) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) {
         const float v = j < 7 ? rp[j] : 0.f;  // the 8th tap meets a zero weight; keep it finite
-        const _Float16 hj = (_Float16)v;
+        const _Float16 hj = split_hi(v);
         h[j] = hj;
-        l[j] = (_Float16)((v - (float)hj) * 2048.f);
+        l[j] = split_lo(v, hj);
       }
       *reinterpret_cast<half8*>(il + e * 16) = h;
       *reinterpret_cast<half8*>(il + (kRows * kTW + e) * 16) = l;
@@ -137,9 +131,8 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(StemParams p) {
       for (int c = 0; c < 2; ++c) {
         const half8 a_hi = *reinterpret_cast<const half8*>(wl + ((((s * 2 + 0) * 2 + half) * 64) + c * 32 + l31) * 16);
         const half8 a_lo = *reinterpret_cast<const half8*>(wl + ((((s * 2 + 1) * 2 + half) * 64) + c * 32 + l31) * 16);
-        acc_h[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_hi, acc_h[c], 0, 0, 0);
-        acc_x[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_hi, b_lo, acc_x[c], 0, 0, 0);
-        acc_x[c] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a_lo, b_hi, acc_x[c], 0, 0, 0);
+        acc_h[c] = split_mfma_h(acc_h[c], a_hi, b_hi);
+        acc_x[c] = split_mfma_x(acc_x[c], a_hi, a_lo, b_hi, b_lo);
       }
     }
     // D layout of the 32x32 tile: register r of lane (l31, half) = row (co) (r & 3) + 8 (r >> 2) + 4 half, column (pixel) l31
@@ -151,8 +144,8 @@ __global__ __launch_bounds__(256, 2) void stem7x7_kernel(StemParams p) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
           const int co = c * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          const float v = acc_h[c][r] + acc_x[c][r] * (1.f / 2048.f) + bias_r[c][r];
-          op[co * plane] = act_apply(v, p.act);
+          const float v = join(acc_h[c][r], acc_x[c][r]) + bias_r[c][r];
+          op[co * plane] = act_apply(v, act);
         }
     }
   }

@@ -5,10 +5,11 @@
 // All four are one-shot (once per stereo pair) and HBM-bound: each input element is read once per
 // consumer tile (re-reads are L1/L2 hits) and every output element is written exactly once.
 #include "common.h"
+#include "split.h"
 
 namespace {
 
-using f32x16 = __attribute__((ext_vector_type(16))) float;
+using namespace as;  // split.h: vector types, operand split / join, bload
 
 // ------------------------------------------------------------------------------------------------
 // corr[b,y,x1,x2] = sum_c f1[b,c,y,x1] f2[b,c,y,x2]  — one (b,y) row is a (W1 x C)·(C x W2) GEMM.
@@ -34,10 +35,6 @@ constexpr int kKS = 48;  // k-steps (channel pairs) held in registers per pass: 
 // no branches around loads, a whole fragment (48 loads) is in flight at once.  The B fragment of
 // N-tile j+1 is fetched while the 48 MFMAs of tile j run (one wave per SIMD at 960x540: latency must
 // be hidden inside the wave, not by occupancy).
-__device__ __forceinline__ float bload(__amdgpu_buffer_rsrc_t r, unsigned voff) {
-  return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(r, (int)voff, 0, 0));
-}
-
 
 // Epilogue shared by the three build kernels: write one 32x32 tile of level 0 and its pooled levels
 // straight from the MFMA accumulator layout (col = lane&31 = x2, row = (r&3) + 8 (r>>2) + 4 (lane>>5)).
@@ -178,23 +175,9 @@ __global__ __launch_bounds__(256) void corr_build_kernel(CorrParams p) {
 // product stops being matrix-core bound (fp32 MFMA needs >= 11 us at 960x540 even at 100 % utilisation)
 // and becomes the HBM-bound stream it should be.  Requires |v| < 65504 (fp16 range): feature maps are
 // O(1).  Operand k-layout of v_mfma_f32_32x32x16_f16: lane (r = l&31, h = l>>5) holds k = 8h..8h+7.
-using half8 = __attribute__((ext_vector_type(8))) _Float16;
 constexpr int kKS16 = 6;  // 16-channel k-steps per pass (96 channels)
 
 __device__ unsigned g_split_overflow_vol;  // as_volumes_split_overflow
-
-// x = hi + lo/2048; with fp16_saturate_mode() (common.h) an operand outside fp16's range saturates instead of becoming
-// inf / NaN; `amax` collects max |x| for the out-of-range count
-__device__ __forceinline__ void split8(const float (&v)[8], half8& hi, half8& lo, float& amax) {
-#pragma unroll
-  for (int j = 0; j < 8; j += 2) amax = fmaxf(amax, fmaxf(fabsf(v[j]), fabsf(v[j + 1])));
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const _Float16 h = (_Float16)v[j];
-    hi[j] = h;
-    lo[j] = (_Float16)((v[j] - (float)h) * 2048.f);
-  }
-}
 
 template <bool A_RESIDENT>
 __global__ __launch_bounds__(256, 2) void corr_build_f16x3_kernel(CorrParams p) {
@@ -234,7 +217,8 @@ __global__ __launch_bounds__(256, 2) void corr_build_f16x3_kernel(CorrParams p) 
 #pragma unroll
       for (int j = 0; j < 8; ++j)
         v[j] = bload(r1, a_off == kOOB ? kOOB : a_off + (unsigned)((ps * kKS16 + s) * 16 + j) * cstr1);
-      split8(v, ahi[s], alo[s], ovf_amax);
+      ovf_amax = amax8(v, ovf_amax);
+      split_mode8(v, ahi[s], alo[s]);
     }
   };
   if (A_RESIDENT) load_a(0);
@@ -258,15 +242,15 @@ __global__ __launch_bounds__(256, 2) void corr_build_f16x3_kernel(CorrParams p) 
         for (int j = 0; j < 8; ++j)
           bv[j] = bload(r2, bo == kOOB ? kOOB : bo + (unsigned)((ps * kKS16 + s) * 16 + j) * cstr2);
         half8 bhi, blo;
-        split8(bv, bhi, blo, ovf_amax);
-        acc_hh = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[s], bhi, acc_hh, 0, 0, 0);
-        acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[s], blo, acc_x, 0, 0, 0);
-        acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo[s], bhi, acc_x, 0, 0, 0);
+        ovf_amax = amax8(bv, ovf_amax);
+        split_mode8(bv, bhi, blo);
+        acc_hh = split_mfma_h(acc_hh, ahi[s], bhi);
+        acc_x = split_mfma_x(acc_x, ahi[s], alo[s], bhi, blo);
       }
     }
     f32x16 res;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) res[r] = acc_hh[r] + acc_x[r] * (1.f / 2048.f);
+    for (int r = 0; r < 16; ++r) res[r] = join(acc_hh[r], acc_x[r]);
     store_pyramid_tile(p, tout, res, nt, lane);
   }
   as::note_split_overflow(ovf_amax, &g_split_overflow_vol);
@@ -334,7 +318,8 @@ __global__ __launch_bounds__(256, 2) void corr_build_lds_kernel(CorrParams p) {
   for (int i = 0; i < kKS16; ++i) {
     if (i < ksteps) {
       half8 hi, lo;
-      split8(bv[i], hi, lo, ovf_amax);
+      ovf_amax = amax8(bv[i], ovf_amax);
+      split_mode8(bv[i], hi, lo);
       const int g = (tid >> 7) + 2 * i;
       const unsigned o = (unsigned)(((g >> 1) * (kNB * 32) + xx) * 32 + (g & 1) * 16);
       *reinterpret_cast<half8*>(corr_smem + o) = hi;
@@ -343,7 +328,10 @@ __global__ __launch_bounds__(256, 2) void corr_build_lds_kernel(CorrParams p) {
   }
   half8 ahi[kKS16], alo[kKS16];
 #pragma unroll
-  for (int s = 0; s < kKS16; ++s) split8(av[s], ahi[s], alo[s], ovf_amax);
+  for (int s = 0; s < kKS16; ++s) {
+    ovf_amax = amax8(av[s], ovf_amax);
+    split_mode8(av[s], ahi[s], alo[s]);
+  }
   __syncthreads();
   if (mt >= p.MT) return;
 
@@ -361,14 +349,13 @@ __global__ __launch_bounds__(256, 2) void corr_build_lds_kernel(CorrParams p) {
       if (s == 0 || s < ksteps) {
         const half8 bhi = *reinterpret_cast<const half8*>(corr_smem + fo + (unsigned)s * (kNB * 32 * 32));
         const half8 blo = *reinterpret_cast<const half8*>(corr_smem + lo_base + fo + (unsigned)s * (kNB * 32 * 32));
-        acc_hh = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[s], bhi, acc_hh, 0, 0, 0);
-        acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(ahi[s], blo, acc_x, 0, 0, 0);
-        acc_x = __builtin_amdgcn_mfma_f32_32x32x16_f16(alo[s], bhi, acc_x, 0, 0, 0);
+        acc_hh = split_mfma_h(acc_hh, ahi[s], bhi);
+        acc_x = split_mfma_x(acc_x, ahi[s], alo[s], bhi, blo);
       }
     }
     f32x16 res;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) res[r] = acc_hh[r] + acc_x[r] * (1.f / 2048.f);
+    for (int r = 0; r < 16; ++r) res[r] = join(acc_hh[r], acc_x[r]);
     store_pyramid_tile(p, tout, res, nt, lane);
   }
   as::note_split_overflow(ovf_amax, &g_split_overflow_vol);
@@ -675,14 +662,6 @@ int as_disparity_regression(const float* cost, float* out, int B, int D, int H, 
   return as::check_launch("disparity_regression");
 }
 
-unsigned as_volumes_split_overflow(int reset) {
-  unsigned v = 0;
-  if (hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_split_overflow_vol), sizeof(v)) != hipSuccess) return 0xFFFFFFFFu;
-  if (reset && v) {
-    const unsigned z = 0;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_split_overflow_vol), &z, sizeof(z));
-  }
-  return v;
-}
+unsigned as_volumes_split_overflow(int reset) { return as::read_reset_counter(&g_split_overflow_vol, reset); }
 
 }  // extern "C"

@@ -26,12 +26,15 @@
 // wgrad_finish_kernel sums the ranges in a fixed order (deterministic, no atomics).  The bias gradient rides along as one
 // extra column tile of ones in the blocks of the first channel tile.
 #include "common.h"
+#include "split.h"
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf8;
-typedef __attribute__((ext_vector_type(16))) float acc16;
-typedef __attribute__((ext_vector_type(4))) float f4;
+using bf8 = as::bf16x8;  // the vector types live in split.h
+using acc16 = as::f32x16;
+using f4 = as::f32x4;
+using u4 = as::u32x4;
+using u2 = as::u32x2;
 
 constexpr int kWgradMaxTensors = 32;
 struct WgradParams {
@@ -50,8 +53,6 @@ struct WgradParams {
   int dbg;           // timing ablations (AS_WGRAD_DBG): 1 = loaders only meet the barriers, 2 = consumers only meet the barriers
 };
 
-typedef __attribute__((ext_vector_type(4))) unsigned int u4;
-typedef __attribute__((ext_vector_type(2))) unsigned int u2;
 struct B3 { bf8 k[3]; };  // the fragments of the taps kx = 0, 1, 2 of one row
 
 // D = elements e0..e7 (aligned), L = (e-2, e-1), R = (e8, e9): kx = 1 is D, kx = 0 / 2 are D shifted by one element
