@@ -30,6 +30,8 @@ def _build_py(tree):
 
 
 _LOCAL = re.compile(r"\.L([A-Za-z_]+?)\d+")  # .LBB12_3 -> .LBB_3: the function's index in the file is not part of its code
+_LOOPREF = re.compile(r"\bBB\d+_")             # the same index in the loop comments ("Parent Loop BB12_3 Depth=1")
+_PAD = re.compile(r"[ \t]+")                   # ... whose column padding shrinks when the index gains a digit
 
 
 def symbols(path):
@@ -39,7 +41,7 @@ def symbols(path):
         if "-- Begin function " in line:
             name, lines = line.split("-- Begin function ")[1].strip(), []
         elif "-- End function" in line and name:
-            out[name] = hashlib.sha1(_LOCAL.sub(r".L\1", "".join(lines)).encode()).hexdigest()
+            out[name] = hashlib.sha1(_PAD.sub(" ", _LOOPREF.sub("BB_", _LOCAL.sub(r".L\1", "".join(lines)))).encode()).hexdigest()
             name = None
         elif name:
             lines.append(line)

@@ -5,6 +5,8 @@ has disparity k everywhere, so the right view's ground truth is k as well.  One 
     python tools/evaluate.py --pairs 4 --prep host                  # down-scale / pad / query grid with torch ops and a host-built grid
     python tools/evaluate.py --pairs 4 --uint8                      # 8-bit images as a loader delivers them (--prep device only)
     python -m torch.distributed.run --nproc-per-node 2 tools/evaluate.py --pairs 8       # pairs sharded over the ranks
+    python tools/evaluate.py --pairs 2 --model-max-disp 256         # the model built for disparities up to 256 (volume of D = 64, the
+                                                                    # largest as_gwc_volume_fwd serves; above it the library's error)
     python tools/evaluate.py --pairs 2 --save-images out/           # disp_{i}.png (colour map) and error_{i}.png per pair; --enc16 adds
                                                                     # the 16-bit disp16_{i}.png, --image-limit N stops after N pairs
 
@@ -24,7 +26,13 @@ sys.path[:0] = [ROOT, os.path.join(ROOT, "any-stereo_amd")]
 import torch  # noqa: E402
 
 
-def main():
+def model_args(a):
+    """The model's construction arguments for the parsed command line `a`: default_args, with --model-max-disp as max_disp."""
+    from anystereo.models import default_args
+    return default_args(a.model) if a.model_max_disp is None else default_args(a.model, max_disp=a.model_max_disp)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--model", default="continuous_IGEVStereo", choices=["continuous_IGEVStereo", "continuous_RAFTStereo"])
     ap.add_argument("--protocol", default="things", choices=["things", "kitti", "middlebury", "eth3d"])
@@ -34,7 +42,10 @@ def main():
     ap.add_argument("--shift", type=int, default=6)
     ap.add_argument("--scale", type=float, default=1.5)
     ap.add_argument("--iters", type=int, default=8)
-    ap.add_argument("--max-disp", type=float, default=None)
+    ap.add_argument("--max-disp", type=float, default=None, help="the evaluator's: additionally count only gt < this value")
+    ap.add_argument("--model-max-disp", type=int, default=None, metavar="N",
+                    help="the model's disparity range (IGEV: the geometry volume holds N/4 disparities; a multiple of 32, at most 256 today); "
+                         "default: default_args' value")
     ap.add_argument("--prep", default="device", choices=["host", "device"],
                     help="device: as_prepare_pair + as_query_grid (two launches); host: query.pad_for_multi_train + upload of the grid")
     ap.add_argument("--uint8", action="store_true", help="feed the images as uint8 (rounded); needs --prep device")
@@ -43,14 +54,18 @@ def main():
                          "ranks each writes into DIR/rank<r>")
     ap.add_argument("--image-limit", type=int, default=None, help="stop writing pictures after this many pairs (per rank)")
     ap.add_argument("--enc16", action="store_true", help="with --save-images: also the 16-bit disparity PNG (disparity * 256)")
-    a = ap.parse_args()
+    return ap.parse_args(argv)
+
+
+def main():
+    a = parse_args()
 
     from anystereo import _lib
     from anystereo.harness import dist
     from anystereo.harness.evaluate import Evaluator, evaluate
     from anystereo.harness.images import ImageSink
     from anystereo.harness.synthetic import fill_module_deterministic, synthetic_pair
-    from anystereo.models import __models__, default_args
+    from anystereo.models import __models__
 
     if not torch.cuda.is_available():
         raise SystemExit("tools/evaluate.py needs a GPU: the models' hot path has no CPU fallback")
@@ -62,7 +77,7 @@ def main():
     dist.init("gloo")  # the only traffic is the merge of the per-image rows: a few KB from host memory
     _lib.load()
 
-    args = default_args(a.model)
+    args = model_args(a)
     model = __models__[a.model](args).eval()
     fill_module_deterministic(model, base_seed=1)
     model = model.to(dev)
@@ -103,7 +118,7 @@ def main():
         print(json.dumps({"tool": "evaluate", "model": a.model, "protocol": a.protocol, "n_gpus": world, "pairs": a.pairs,
                           "size": [a.height, a.width], "scale": a.scale, "prep": a.prep,
                           "image_dtype": "uint8" if a.uint8 else "float32", "iters": a.iters, "gt_disparity": a.shift,
-                          "weights": "deterministic fill", "pairs_per_s": round(sum(rates), 3),
+                          "weights": "deterministic fill", "model_max_disp": args.max_disp, "pairs_per_s": round(sum(rates), 3),
                           "per_rank_pairs_per_s": [round(r, 3) for r in rates], "rank0_pairs": local_pairs,
                           "library": _lib.library_info(), **({"images_written": int(sum(written))} if sink is not None else {}),
                           **merged}))
