@@ -128,6 +128,9 @@ SIGNATURES = {
     "as_convex_upsample_quater": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "as_convex_upsample_quater_bwd": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "as_affinity_bwd": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "as_affinity_window_ws_bytes": (C.c_int64, [_i, _i, _i]),
+    "as_affinity_window": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp]),
+    "as_affinity_window_bwd": (_i, [_vp, _vp, C.c_int64, _vp, C.c_int64, _vp, C.c_int64, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "as_liif_affinity": (_i, [_pp, C.POINTER(C.c_int), _i, _vp, _vp, _i, _i, _i, _vp]),
     "as_liif_affinity_ws_bytes": (C.c_int64, [_i, _i, _i, _i]),
     "as_liif_lowres_pack_bytes": (C.c_int64, [_i]),

@@ -185,13 +185,13 @@ class InitDispHead(torch.autograd.Function):
 # ---- a12/a13: cat(x, affinity(x.detach())) (liif.py:496-499) ----------------------------------------------------
 class StructureFeature(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, x):
+    def forward(ctx, x, win=3):
         ctx.c = x.shape[1]
-        return ops.structure_feature(x)
+        return ops.structure_feature(x) if win == 3 else ops.affinity_window(x, win, True)
 
     @staticmethod
     def backward(ctx, d_out):
-        return d_out[:, :ctx.c].contiguous()  # the affinity is computed on x.detach()
+        return d_out[:, :ctx.c].contiguous(), None  # the affinity is computed on x.detach()
 
 
 # ---- a14: nearest gather + relative coordinates (liif.py:108-137) -----------------------------------------------
@@ -803,21 +803,27 @@ class InterpBilinear(torch.autograd.Function):
 # ---- §8 f4: off-by-default upsampler options (csrc/liif_variants.hip) ---------------------------------------------------
 class StructureFeatureLive(torch.autograd.Function):
     """cat(x, affinity(x)) / affinity(x) with the affinity of the LIVE map ('with_ISU', 'with_1_4ISU', 'only_ISU',
-    liif.py:493-495,501-503,534-535): the gradient reaches x through F.normalize and the eight dot products."""
+    liif.py:493-495,501-503,534-535): the gradient reaches x through F.normalize and the win*win - 1 dot products (win = 3: the
+    3x3 kernels; 5, 7: csrc/affinity_window.hip)."""
 
     @staticmethod
-    def forward(ctx, x, with_x):
-        out = ops.structure_feature(x)
-        if not with_x:
-            out = out[:, x.shape[1]:].contiguous()
+    def forward(ctx, x, with_x, win=3):
+        if win == 3:
+            out = ops.structure_feature(x)
+            if not with_x:
+                out = out[:, x.shape[1]:].contiguous()
+        else:
+            out = ops.affinity_window(x, win, bool(with_x))
         ctx.save_for_backward(x, out)
-        ctx.with_x = bool(with_x)
+        ctx.with_x, ctx.win = bool(with_x), win
         return out
 
     @staticmethod
     def backward(ctx, d_out):
         x, out = ctx.saved_tensors
-        return ops.affinity_backward(x, out, _c(d_out), ctx.with_x), None
+        if ctx.win == 3:
+            return ops.affinity_backward(x, out, _c(d_out), ctx.with_x), None, None
+        return ops.affinity_window_backward(x, out, _c(d_out), ctx.win, ctx.with_x), None, None
 
 
 class LiifLatent(torch.autograd.Function):

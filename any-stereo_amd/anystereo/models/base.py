@@ -54,7 +54,10 @@ class ContinuousStereoBase(nn.Module):
         return BasicMultiUpdateBlock(args, hidden_dims=args.hidden_dims, geo_channels=self.geo_channels)
 
     def _make_liif(self, args, indim, chanels):
-        aff = {"win_w": args.lsp_width, "win_h": args.lsp_height, "dilation": args.lsp_dilation}
+        # continuous_IGEVstereo.py:163-164 takes the window from (lsp_width, lsp_height); prune_raft_stereo.py:184-185 sets BOTH
+        # sides from lsp_width and never reads lsp_height
+        win_h = args.lsp_height if self.geo_channels > 0 else args.lsp_width
+        aff = {"win_w": args.lsp_width, "win_h": win_h, "dilation": args.lsp_dilation}
         return liif_out_multi_scale_Training(
             encoder_dim=indim, mlphidden_list=args.mlphidden_list, pos_dim=args.pos_dim, pos_enconding=args.pos_enconding,
             pos_enconding_new=args.pos_enconding_new, local_ensemble=args.local_ensemble, decode_cell=args.decode_cell,

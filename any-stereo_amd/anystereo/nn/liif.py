@@ -7,7 +7,8 @@ The default configuration (unfold_similarity='with_v2ISU', pos_dim=0) takes the 
 reference can run ('with_ISU', 'with_1_4ISU', 'with_embed_ISU', 'only_ISU', 'only_unfold', no structure feature, Fourier
 position encoding fixed or learned, cell decoding, quarter-nearest sampling, three inputs) takes the general latent builder
 (csrc/liif_variants.hip), pinned by tests/golden/liif_variants.npz.  Option sets the reference itself cannot run build the same
-parameters and fail at forward (see _DEAD).
+parameters and fail at forward (see _DEAD).  The affinity window (lsp_width = lsp_height) is 3, 5 or 7: 3x3 takes the kernels
+above; 5x5 and 7x7 take csrc/affinity_window.hip and the staged upsampler (tests/golden/liif_windows.npz), never the fused tail.
 
 Data layout: the per-query latent is built CHANNEL-major, latent[B, 228, Q], so that
   * the gather kernel's stores are coalesced along Q,
@@ -78,23 +79,37 @@ _DEAD = {
                "'with_3v2ISU' modes)",
     "pos_enconding_new": "pos_enconding_new: PositionEncoder is built with enc_dims = 2 (liif.py:591-592 after :588), its "
                          "frequency table is empty and the projection at liif.py:274 raises",
+    "non_square": "AffinityFeature with win_h != win_w: the reference pads by win_w//2 on BOTH axes (liif.py:424,436-437), its "
+                  "Unfold then does not yield H*W windows and the reshape at liif.py:438 raises",
+    "embed_window": "with_embed_ISU with a window other than 3x3: sfc_embeding is built for input_chanels + 8 channels whatever the "
+                    "window (liif.py:491), so its 1x1 convolution at liif.py:527 raises on the input_chanels + win_h*win_w - 1 "
+                    "channels it is handed",
 }
+
+WINDOWS = ops.AFFINITY_WINDOWS  # (3, 5, 7): square windows the kernels are built for (lsp_width = lsp_height); 3 is the reference's default
 
 
 class AffinityFeature(nn.Module):
-    """3x3 cosine affinity to the 8 neighbours (liif.py:417-446).  Dilation 1 is the only window the reference can evaluate."""
+    """Cosine affinity to the win*win - 1 neighbours of a square window (liif.py:417-446).  Dilation 1 is the only one the
+    reference can evaluate; a non-square window constructs (the MLP width follows win_h*win_w - 1) and fails at forward like
+    the reference."""
 
     def __init__(self, win_h, win_w, dilation, cut):
         super().__init__()
-        if (win_h, win_w) != (3, 3):
-            raise NotImplementedError("AffinityFeature: only the 3x3 window (lsp_width = lsp_height = 3) is built")
+        if win_h == win_w and win_w not in WINDOWS:
+            raise NotImplementedError(f"AffinityFeature: a {win_h}x{win_w} window is not built; lsp_width = lsp_height must be one "
+                                      f"of {WINDOWS}")
         self.win_w, self.win_h, self.dilation, self.cut = win_w, win_h, dilation, 0
         self._padding = win_w // 2
 
     def forward(self, feature):
         if self.dilation != 1:
             raise RuntimeError(_DEAD["dilated"])
+        if self.win_h != self.win_w:
+            raise RuntimeError(_DEAD["non_square"])
         x = feature.float().contiguous()
+        if self.win_w != 3:
+            return G.StructureFeatureLive.apply(x, False, self.win_w) if G.needs_grad(x) else ops.affinity_window(x, self.win_w, False)
         if G.needs_grad(x):
             return G.StructureFeatureLive.apply(x, False)
         return ops.structure_feature(x)[:, x.shape[1]:]
@@ -147,6 +162,8 @@ class StructureFeature(nn.Module):
         u = self.unfold
         x = x.float().contiguous()
         grad = G.needs_grad(x)
+        if (self.win_h, self.win_w) != (3, 3) and any(k in u for k in ("with_ISU", "with_1_4ISU", "with_v2ISU", "with_embed_ISU", "only_ISU")):
+            return self._forward_window(x, grad)
         if "with_ISU" in u or "with_1_4ISU" in u:
             return G.StructureFeatureLive.apply(x, True) if grad else ops.structure_feature(x)
         if "with_v2ISU" in u:
@@ -163,6 +180,19 @@ class StructureFeature(nn.Module):
         if any(k in u for k in ("Dila_", "with_1_43", "with_3v2ISU")):
             raise RuntimeError(_DEAD["dilated"])
         return x  # liif.py:492-572 falls through to `return x` for any other string
+
+    def _forward_window(self, x, grad):
+        """The same modes with a window other than 3x3 (csrc/affinity_window.hip); what the reference cannot run raises."""
+        u, win = self.unfold, self.win_w
+        if self.win_h != self.win_w:
+            raise RuntimeError(_DEAD["non_square"])
+        if "with_ISU" in u or "with_1_4ISU" in u:
+            return G.StructureFeatureLive.apply(x, True, win) if grad else ops.affinity_window(x, win, True)
+        if "with_v2ISU" in u:
+            return G.StructureFeature.apply(x, win) if grad else ops.affinity_window(x, win, True)
+        if "with_embed_ISU" in u:
+            raise RuntimeError(_DEAD["embed_window"])
+        return self.Affi1(x)  # only_ISU
 
 
 class SpatialEncoding(nn.Module):
@@ -317,6 +347,9 @@ class liif_out_multi_scale_Training(nn.Module):
         # latent builder (same function, csrc/liif_variants.hip)
         self._default_variant = (unfold == "with_v2ISU" and not pos_enconding and not pos_enconding_new and not decode_cell
                                  and not local_ensemble and quater_nearest is None)
+        # the one-kernel tail and its early stem_2x rows (csrc/liif_fused.hip) are built around the 8 affinity channels of the 3x3
+        # window; the other windows take the staged path (same function)
+        self.window = (affinity_settings["win_h"], affinity_settings["win_w"])
 
     # ---- general path: any option set the reference can run ---------------------------------------------------------------
     def _structure(self, feats):
@@ -426,7 +459,8 @@ class liif_out_multi_scale_Training(nn.Module):
         """The one-kernel tail exists for the default configuration: <= 2 inputs, MLP 128-64-64-9, split-precision mode,
         inference.  Everything else takes the staged path (same function)."""
         lin = [m for m in self.imnet.layers if isinstance(m, nn.Linear)]
-        return (self.fused_tail and self._default_variant and coord.is_cuda and not torch.is_grad_enabled() and len(feats_parts) in (1, 2)
+        return (self.fused_tail and self._default_variant and self.window == (3, 3) and coord.is_cuda and not torch.is_grad_enabled()
+                and len(feats_parts) in (1, 2)
                 and [tuple(m.weight.shape) for m in lin[1:]] == [(64, 128), (64, 64), (9, 64)] and lin[0].weight.shape[0] == 128
                 and ops.get_precision() == "split" and all(len(ps) <= 2 for ps in feats_parts)
                 and all(p.shape[1] % 16 == 0 for ps in feats_parts for p in ps))
@@ -460,7 +494,7 @@ class liif_out_multi_scale_Training(nn.Module):
         is picked up by the next `upsample_fused` call that sees the same tensors; `clear_static()` drops it."""
         self.__dict__.pop("_early_static", None)
         # only when the fused tail will pick the rows up (fused_ok's conditions that do not depend on the coordinates)
-        if not (self.early_static and self.fused_tail and self._default_variant and 0 < slot < len(feats_parts) <= 2
+        if not (self.early_static and self.fused_tail and self._default_variant and self.window == (3, 3) and 0 < slot < len(feats_parts) <= 2
                 and not torch.is_grad_enabled() and ops.get_precision() == "split"
                 and all(p_.is_cuda and p_.shape[1] % 16 == 0 for ps in feats_parts for p_ in ps)):
             return

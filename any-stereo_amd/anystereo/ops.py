@@ -1817,6 +1817,52 @@ def affinity_backward(x, sf_out, d_out, with_x: bool):
     return dx
 
 
+AFFINITY_WINDOWS = (3, 5, 7)
+
+
+def _req_window(win, what: str) -> int:
+    if isinstance(win, bool) or not isinstance(win, int) or win not in AFFINITY_WINDOWS:
+        raise RuntimeError(f"{what}: win must be one of {AFFINITY_WINDOWS}, got {win!r}")
+    return win
+
+
+def affinity_window(x: torch.Tensor, win: int, with_x: bool) -> torch.Tensor:
+    """Cosine affinity to the win*win - 1 neighbours of a win x win window (liif.py:417-446): [B,win*win-1,H,W], or with_x
+    cat(x, affinity) [B,C+win*win-1,H,W] (:496-499).  The 3x3 call paths use structure_feature; win = 3 is for cross-checks."""
+    _req(x, "x")
+    _req_window(win, "affinity_window")
+    if x.dim() != 4:
+        raise RuntimeError(f"affinity_window: x must be [B,C,H,W], got {tuple(x.shape)}")
+    b, c, h, w = x.shape
+    n = win * win - 1
+    out = torch.empty((b, c + n if with_x else n, h, w), device=x.device, dtype=torch.float32)
+    ws = torch.empty(L.load().as_affinity_window_ws_bytes(b, h, w) // 4, device=x.device, dtype=torch.float32)
+    with _guard(x.device):
+        L.check(L.load().as_affinity_window(_p(x), _p(out), _p(ws), b, c, h, w, win, 1 if with_x else 0, _stream()), "affinity_window")
+    return out
+
+
+def affinity_window_backward(x, out, d_out, win: int, with_x: bool):
+    """Gradient w.r.t. x of affinity_window(x, win, with_x), the affinity taken on the LIVE map.  out / d_out: the forward
+    output and its gradient ([B,C+n,H,W] or [B,n,H,W], n = win*win - 1)."""
+    _req(x, "x"), _req(out, "out"), _req(d_out, "d_out")
+    _req_window(win, "affinity_window_backward")
+    b, c, h, w = x.shape
+    n = win * win - 1
+    ctot = c + n if with_x else n
+    if tuple(out.shape) != (b, ctot, h, w) or tuple(d_out.shape) != (b, ctot, h, w):
+        raise RuntimeError("affinity_window_backward: forward output / gradient shape mismatch")
+    plane = h * w
+    skip = c * plane * 4 if with_x else 0
+    dx = torch.empty_like(x)
+    ws = torch.empty(L.load().as_affinity_window_ws_bytes(b, h, w) // 4, device=x.device, dtype=torch.float32)
+    with _guard(x.device):
+        L.check(L.load().as_affinity_window_bwd(_p(x), out.data_ptr() + skip, ctot * plane, d_out.data_ptr() + skip, ctot * plane,
+                                                _p(d_out) if with_x else None, ctot * plane, _p(dx), _p(ws), b, c, h, w, win,
+                                                _stream()), "affinity_window_bwd")
+    return dx
+
+
 # ------------------------------------------------------------------------------------------------
 # LIIF upsampler, fused inference pipeline (csrc/liif_fused.hip)
 # ------------------------------------------------------------------------------------------------

@@ -608,6 +608,28 @@ int as_convex_upsample_quater_bwd(const float* disp, const float* scale, const f
                                   float* d_mask, float* d_disp, int B, int H, int W, int Q, int mask_is_logits, void* stream);
 int as_affinity_bwd(const float* x, const float* aff, long long aff_batch_stride, const float* g_aff, long long g_aff_batch_stride,
                     const float* g_x, long long g_x_batch_stride, float* dx, float* ws, int B, int C, int H, int W, void* stream);
+/* AffinityFeature with a win x win window, win in {3, 5, 7} (liif.py:417-446 with --lsp_width / --lsp_height; csrc/affinity_window.hip).
+ * With R = win / 2, n = win * win - 1 and xh = x / max(||x||_2 over channels, 1e-12):
+ *   aff[b, j, y, x] = max(0, xh(p) . xh(p + o_j)),  o_j = (ky - R, kx - R) for (ky, kx) row-major with the centre skipped (Unfold's
+ *   order, liif.py:436-441); a neighbour outside the map gives exactly 0.
+ * as_affinity_window      x [B,C,H,W] -> out [B,n,H,W] (with_x == 0) or out [B,C+n,H,W] = cat(x, aff) with x copied through
+ *                  (with_x != 0), written in full by one pass.  ws = as_affinity_window_ws_bytes(B, H, W) bytes of scratch (the
+ *                  clamped norms, written by a first small launch).  A block owns a 16x16 pixel tile and its halo of R and stages
+ *                  the normalised channels in LDS in chunks of 8; a pixel's n sums stay in registers.
+ * as_affinity_window_bwd  gradient w.r.t. x of the same function on the LIVE map ('with_ISU', 'with_1_4ISU', 'only_ISU'): with
+ *                  w_j(p) = [aff_j(p) > 0] g_j(p) + [aff_(n-1-j)(p + o_j) > 0] g_(n-1-j)(p + o_j),
+ *                  dx_c(p) = (sum_j w_j(p) xh_c(p + o_j) - xh_c(p) sum_j w_j(p) aff_j(p)) / max(||x(p)||, 1e-12)  (+ g_x).
+ *                  aff / g_aff point at the n affinity channels of the forward output and of its gradient (batch strides in
+ *                  floats, as in as_affinity_bwd); g_x [C channels] or NULL is the pass-through gradient of the concat; ws as
+ *                  above.  Every thread gathers for its own pixel: no atomics, the same bits on every run.
+ * win == 3 is accepted for cross-checking; the 3x3 call paths keep as_structure_feature / as_affinity_bwd.
+ * AS_ERR_BAD_ARG: a NULL pointer, a non-positive size, win outside {3, 5, 7}.  AS_ERR_BAD_SHAPE: H * W >= 2^31, a tensor of 2^63
+ * bytes or more, a batch stride smaller than the tensor it strides over.  Checked before any device call. */
+int64_t as_affinity_window_ws_bytes(int B, int H, int W);
+int as_affinity_window(const float* x, float* out, float* ws, int B, int C, int H, int W, int win, int with_x, void* stream);
+int as_affinity_window_bwd(const float* x, const float* aff, long long aff_batch_stride, const float* g_aff,
+                           long long g_aff_batch_stride, const float* g_x, long long g_x_batch_stride, float* dx, float* ws, int B,
+                           int C, int H, int W, int win, void* stream);
 
 /* f4: the encoders' 7x7, 3 -> 64 channel stem (`conv1`, extractor.py:127 in BasicEncoder / MultiBasicEncoder; stride 1, padding 3)
  *   as one split-precision MFMA launch (csrc/stem7x7.hip): out [B,64,H,W] = act(conv7x7(x [B,3,H,W]) + bias).

@@ -7,6 +7,7 @@ has disparity k everywhere, so the right view's ground truth is k as well.  One 
     python -m torch.distributed.run --nproc-per-node 2 tools/evaluate.py --pairs 8       # pairs sharded over the ranks
     python tools/evaluate.py --pairs 2 --model-max-disp 256         # the model built for disparities up to 256 (volume of D = 64, the
                                                                     # largest as_gwc_volume_fwd serves; above it the library's error)
+    python tools/evaluate.py --pairs 2 --lsp-window 5               # the upsampler built with a 5x5 affinity window (3, 5 or 7)
     python tools/evaluate.py --pairs 2 --save-images out/           # disp_{i}.png (colour map) and error_{i}.png per pair; --enc16 adds
                                                                     # the 16-bit disp16_{i}.png, --image-limit N stops after N pairs
 
@@ -27,9 +28,13 @@ import torch  # noqa: E402
 
 
 def model_args(a):
-    """The model's construction arguments for the parsed command line `a`: default_args, with --model-max-disp as max_disp."""
+    """The model's construction arguments for the parsed command line `a`: default_args, with --model-max-disp as max_disp and
+    --lsp-window as lsp_width = lsp_height."""
     from anystereo.models import default_args
-    return default_args(a.model) if a.model_max_disp is None else default_args(a.model, max_disp=a.model_max_disp)
+    over = {} if a.model_max_disp is None else {"max_disp": a.model_max_disp}
+    if a.lsp_window is not None:
+        over.update(lsp_width=a.lsp_window, lsp_height=a.lsp_window)
+    return default_args(a.model, **over)
 
 
 def parse_args(argv=None):
@@ -46,6 +51,9 @@ def parse_args(argv=None):
     ap.add_argument("--model-max-disp", type=int, default=None, metavar="N",
                     help="the model's disparity range (IGEV: the geometry volume holds N/4 disparities; a multiple of 32, at most 256 today); "
                          "default: default_args' value")
+    ap.add_argument("--lsp-window", type=int, default=None, metavar="N", choices=[3, 5, 7],
+                    help="the upsampler's affinity window, lsp_width = lsp_height = N (3, 5 or 7; 5 and 7 take the staged upsampler); "
+                         "default: default_args' 3")
     ap.add_argument("--prep", default="device", choices=["host", "device"],
                     help="device: as_prepare_pair + as_query_grid (two launches); host: query.pad_for_multi_train + upload of the grid")
     ap.add_argument("--uint8", action="store_true", help="feed the images as uint8 (rounded); needs --prep device")
@@ -118,7 +126,7 @@ def main():
         print(json.dumps({"tool": "evaluate", "model": a.model, "protocol": a.protocol, "n_gpus": world, "pairs": a.pairs,
                           "size": [a.height, a.width], "scale": a.scale, "prep": a.prep,
                           "image_dtype": "uint8" if a.uint8 else "float32", "iters": a.iters, "gt_disparity": a.shift,
-                          "weights": "deterministic fill", "model_max_disp": args.max_disp, "pairs_per_s": round(sum(rates), 3),
+                          "weights": "deterministic fill", "model_max_disp": args.max_disp, "lsp_window": [args.lsp_height, args.lsp_width], "pairs_per_s": round(sum(rates), 3),
                           "per_rank_pairs_per_s": [round(r, 3) for r in rates], "rank0_pairs": local_pairs,
                           "library": _lib.library_info(), **({"images_written": int(sum(written))} if sink is not None else {}),
                           **merged}))
