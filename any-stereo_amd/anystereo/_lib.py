@@ -180,6 +180,7 @@ SIGNATURES = {
     "as_lr_consistency": (_i, [_vp, _vp, _vp, _i, _i, _i, C.c_float, _vp]),
     "as_prepare_pair": (_i, [_vp, _vp, _vp, _vp] + [_i] * 10 + [_vp]),
     "as_query_grid": (_i, [_vp] + [_i] * 9 + [_vp]),
+    "as_resize_disp": (_i, [_vp, _vp] + [_i] * 9 + [C.c_float, _vp]),
     "as_disp_images": (_i, [_vp] * 5 + [_i] * 3 + [C.c_float] * 3 + [_vp]),
     "as_train_queries_ws_bytes": (C.c_int64, [C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _i]),
     "as_train_queries": (_i, [_pp, C.POINTER(C.c_int), C.POINTER(C.c_int), _i, _i, _i, C.c_uint64, _vp, _vp, _vp, _vp,

@@ -22,7 +22,7 @@ from typing import Optional, Sequence
 import torch
 
 from . import dist
-from .query import pad_for_multi_train, prepare_on_device
+from .query import pad_for_multi_train, prepare_on_device, query_plan, resize_disparity_host
 
 REGIONS = ("all", "noc", "occ")
 METRICS = ("EPE", "D1", "Thres1", "Thres2", "Thres3")
@@ -244,9 +244,34 @@ class Evaluator:
         return out
 
 
+def _field_estimates(model, i1, i2, coord, sc, iters, ks, baseline, scale, divis_by, h, w):
+    """[N,B,H,W]: the curve's iterations and the baseline of one padded pair, from ONE encoded pass."""
+    from .. import ops
+    bs = i1.shape[0]
+    field = model.encode(i1, i2, iters=iters, at=ks)
+    ests = [field.query(coord.clone(), sc, at=k).reshape(bs, h, w) for k in ks]
+    if baseline == "bicubic":
+        h_pad, w_pad = i1.shape[-2:]
+        plan = query_plan(h, w, scale, divis_by)  # the pair's geometry: where the low-resolution frame lies inside the padded one
+        if (plan.h_pad, plan.w_pad) != (h_pad, w_pad):
+            raise RuntimeError(f"evaluate: the padded pair is {h_pad}x{w_pad}, query_plan gives {plan.h_pad}x{plan.w_pad}")
+        one = query_plan(h_pad, w_pad, 1.0, divis_by)  # the padded frame queried at its own pixels: no padding, no resize
+        if i1.is_cuda:
+            grid = ops.query_grid(one, bs, i1.device)
+        else:
+            from .query import query_grid_host
+            grid = query_grid_host(one, bs, i1.device)
+        low = field.query(grid, torch.ones_like(sc)).reshape(bs, h_pad, w_pad)
+        crop, size = (plan.pad[0], plan.pad[2], plan.h_lr, plan.w_lr), (h, w)
+        ests.append(ops.resize_disparity(low, crop, size, float(scale)) if low.is_cuda
+                    else resize_disparity_host(low, crop, size, float(scale)))
+    return torch.stack(ests, 0)
+
+
 @torch.no_grad()
 def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", max_disp: Optional[float] = None, thres=(1, 2, 3),
-             divis_by: int = 32, evaluator: Optional[Evaluator] = None, prep: str = "host", images=None) -> dict:
+             divis_by: int = 32, evaluator: Optional[Evaluator] = None, prep: str = "host", images=None, curve=None,
+             baseline: Optional[str] = None) -> dict:
     """Run `model` over `pairs` as the reference's validate_* loops do (evaluation.py:341-373): down-scale by `scale` and pad
     (`query.pad_for_multi_train`), query the full-resolution grid in test_mode, reshape [B,1,Q] -> [B,H,W] and feed an Evaluator.
 
@@ -261,10 +286,28 @@ def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", ma
     the timed span); the result gains "images_written".  The sink's pinned host buffers are allocated inside the loop, once per
     batch until its first flush (reused afterwards): that allocation is in the timed span.  With None nothing changes.
 
-    Only the last GRU iteration is evaluated: in test_mode the models up-sample the final disparity alone
-    (continuous_IGEVstereo.py:267-268), so a per-iteration curve would cost one up-sampling pass per iteration."""
+    With `curve` and `baseline` at None only the last GRU iteration is evaluated, by the model's forward: in test_mode the models
+    up-sample the final disparity alone (continuous_IGEVstereo.py:267-268).
+    curve: 1-based GRU iterations, each at most `iters`, e.g. (4, 8, 16, 32): the pass is encoded ONCE per batch
+    (`model.encode(..., at=curve)`) and every iteration of the curve is one more query of that field — accuracy per iteration for
+    one loop instead of one evaluation per candidate `iters`.
+    baseline: "bicubic" = the interpolation baseline of the reference's `multi_evaothers` branch (evaluation.py:91-100, :125-146):
+    the disparity at scale 1 on the padded low-resolution frame — here a second query of the same field, the model's OWN scale-1
+    output; other fixed-scale networks are not built — un-padded, multiplied by `scale` and resized bicubically to the full
+    frame (`ops.resize_disparity`).  It is the protocol the continuous output is meant to beat.
+    With either option the estimates are, in order, the curve's iterations (`iters` alone when curve is None) and the baseline;
+    all go into one `Evaluator.update` as [N,B,H,W], the result gains "estimates": ["iter4", ..., "bicubic"], and `images` takes
+    the last continuous estimate.  Still one synchronisation per dataset."""
     if prep not in ("host", "device"):
         raise ValueError(f"evaluate: prep must be 'host' or 'device', got {prep!r}")
+    if baseline not in (None, "bicubic"):
+        raise ValueError(f"evaluate: baseline must be None or 'bicubic', got {baseline!r}")
+    field_mode = curve is not None or baseline is not None
+    if field_mode:
+        ks = (int(iters),) if curve is None else tuple(int(k) for k in curve)
+        if not ks or any(k < 1 or k > int(iters) for k in ks) or list(ks) != sorted(set(ks)):
+            raise ValueError(f"evaluate: curve must be ascending distinct iterations in [1, {int(iters)}], got {curve!r}")
+        names = [f"iter{k}" for k in ks] + ([baseline] if baseline else [])
     ev = evaluator if evaluator is not None else Evaluator(protocol, max_disp=max_disp, thres=thres)
     model.eval()
     n_pairs = 0
@@ -280,18 +323,23 @@ def evaluate(model, pairs, scale: float, iters: int, protocol: str = "kitti", ma
             coord = coord.to(image1.device).unsqueeze(0).expand(bs, *coord.shape).contiguous()
             i1, i2 = i1.contiguous(), i2.contiguous()
         sc = torch.full((bs, 1), float(scale), device=image1.device)
-        pred = model(i1, i2, iters=iters, test_mode=True, hr_coord=coord, scale=sc)
-        est = pred.reshape(1, bs, h, w)
+        if field_mode:
+            est = _field_estimates(model, i1, i2, coord, sc, iters, ks, baseline, scale, divis_by, h, w)
+        else:
+            pred = model(i1, i2, iters=iters, test_mode=True, hr_coord=coord, scale=sc)
+            est = pred.reshape(1, bs, h, w)
         if ev.protocol == "things":
             ev.update(est, gt, valid, gt_right=extra)
         else:
             ev.update(est, gt, valid, noc=extra)
         if images is not None:
-            images.add(est[0], gt)
+            images.add(est[len(ks) - 1] if field_mode else est[0], gt)
         n_pairs += bs
     res = ev.result()  # the one synchronisation
     dt = time.perf_counter() - t0
     res.update(pairs=n_pairs, seconds=dt, pairs_per_s=(n_pairs / dt if dt > 0 else 0.0))
+    if field_mode:
+        res["estimates"] = names
     if images is not None:
         res["images_written"] = len(images.flush())
     return res

@@ -205,6 +205,34 @@ def bicubic_pad_host(image: torch.Tensor, plan: QueryPlan) -> torch.Tensor:
     return out.contiguous()
 
 
+def resize_disparity_host(src: torch.Tensor, crop, size, mul: float = 1.0) -> torch.Tensor:
+    """fp32 [N,Hs,Ws] (or [N,1,Hs,Ws]) -> fp32 [N,H,W] as `as_resize_disp` forms it, in plain torch on any device: the resize of the
+    interpolation baseline (evaluation.py:125-146, `multi_evaothers`), F.interpolate(unpad(x) * scale, (H, W), mode='bicubic').
+    crop = (top, left, hc, wc), size = (H, W).  Each tap is multiplied by `mul` first; the taps are clamped to the crop, never to
+    the padded frame around it; a crop of the output's shape is copied (times mul)."""
+    x = src.float()
+    if x.dim() == 4 and x.shape[1] == 1:
+        x = x[:, 0]
+    top, left, hc, wc = (int(v) for v in crop)
+    h, w = (int(v) for v in size)
+    assert x.dim() == 3 and hc > 0 and wc > 0 and top >= 0 and left >= 0 and top + hc <= x.shape[1] and left + wc <= x.shape[2]
+    x = x[:, top:top + hc, left:left + wc] * float(mul)
+    if (hc, wc) == (h, w):
+        return x.contiguous()
+    iy, wy = _cubic_axis(hc, h, h, 0, x.device)
+    ix, wx = _cubic_axis(wc, w, w, 0, x.device)
+    out = None
+    for a in range(4):
+        rows = x[:, iy[a]]                                       # [N,H,wc]
+        acc = None
+        for b in range(4):
+            term = rows[:, :, ix[b]] * wx[b].view(1, 1, -1)
+            acc = term if acc is None else acc + term
+        term = acc * wy[a].view(1, -1, 1)
+        out = term if out is None else out + term
+    return out.contiguous()
+
+
 def prepare_on_device(image1, image2, scale_test, divis_by: int = 32, fixed: bool = False):
     """The device counterpart of pad_for_multi_train (fixed=False) / pad_for_multi_train_fixed (fixed=True): image1 / image2 [B,3,H,W]
     on the GPU, uint8 or float32 -> (image1_pad, image2_pad fp32 [B,3,h_pad,w_pad], hr_coord [B, Q, 2], p).  Two launches

@@ -281,6 +281,82 @@ class ContinuousStereoBase(nn.Module):
         g.replay()
         return out.clone()
 
+    # ---- a finished pass as a field: query it again (models/field.py) -------------------------------------------------------
+    def encode(self, image1, image2, iters=32, at=None):
+        """The pre-loop and the GRU loop of `forward(test_mode=True)` — the pipelined loop where forward would take it, the generic
+        one otherwise — stopping in front of `upsample_disp` -> a `StereoField`, whose `query(hr_coord, scale)` is that one
+        upsampler pass: any number of query sets, scales and (with `at`) GRU iterations for one loop.
+        at: iterable of 1-based iterations whose (disparity, hidden state) are kept, default (iters,); `iters` is always kept.
+        Inference only: eval mode, no_grad, CUDA tensors.  Under `enable_graph(True)` the loop replays from the graph cache
+        (keyed on `at` as well) and the field holds clones of the graph's outputs; queries stay eager."""
+        from .field import StereoField, normalize_at
+        if self.training:
+            raise RuntimeError("encode: the model is in training mode (fields are inference only: call model.eval())")
+        if torch.is_grad_enabled():
+            raise RuntimeError("encode: gradients are enabled (fields are inference only: use torch.no_grad())")
+        if not (torch.is_tensor(image1) and torch.is_tensor(image2) and image1.is_cuda and image2.is_cuda):
+            raise RuntimeError("encode: image1 / image2 must be CUDA (HIP) tensors — the anystereo hot path has no CPU fallback")
+        iters = int(iters)
+        if iters < 1:
+            raise ValueError(f"encode: iters must be positive, got {iters}")
+        at = normalize_at(at, iters)
+        if self._reduced_precision(image1) and not ops.get_fast_fp16():
+            with ops.fast_fp16(True):
+                return self.encode(image1, image2, iters, at)
+        fingerprint, mode = self._weights_fingerprint(), (ops.get_precision(), ops.get_fast_fp16())
+        if getattr(self, "_use_graph", False):
+            state = self._encode_graphed(image1, image2, iters, at, fingerprint)
+        else:
+            state = self._encode_impl(image1, image2, iters, at)
+        return StereoField(self, iters, at, state, fingerprint, mode)
+
+    def _encode_impl(self, image1, image2, iters, at):
+        """-> {"disp": [..], "net": [..] per kept iteration, "stems": (stem_4x, stem_2x, stem_1x)}: copies owned by the caller.
+        The loop's kernels write every iteration's disparity and hidden state into fresh tensors (nothing is updated in place or
+        ping-ponged), so the copies are not needed for the values; they give the field storage of its own — on the stream that
+        produced the tensor, recorded for the stream that queries — without the blocked twin a hidden state carries and without
+        the second half of the batched stems."""
+        req = {"keep": {k: {} for k in at}}
+        self.__dict__["_encode_request"] = req
+        try:
+            self._forward_impl_marked(image1, image2, iters=iters, test_mode=True, hr_coord=None, scale=1.0)
+        finally:
+            self.__dict__.pop("_encode_request", None)
+        stems = tuple(None if t is None else t.clone() for t in req["stems"])
+        return {"disp": [req["keep"][k]["disp"] for k in at], "net": [req["keep"][k]["net"] for k in at], "stems": stems}
+
+    def _encode_graphed(self, image1, image2, iters, at, fingerprint):
+        """`_forward_graphed` for the loop alone: the same cache, LRU rule, warm-up and memset rewrite; the key carries `at`."""
+        key = ("encode", tuple(image1.shape), tuple(at), int(iters), image1.device.index, ops.get_precision(),
+               ops.get_fast_fp16() or bool(getattr(self.args, "mixed_precision", False)), fingerprint,
+               id(self.__dict__.get("stamps")))
+        graphs = self.__dict__.setdefault("_graphs", {})
+        ent = graphs.pop(key, None)
+        if ent is None:
+            while len(graphs) >= max(1, self.graph_cache_size):
+                graphs.pop(next(iter(graphs)))
+            st = [t.detach().clone() for t in (image1, image2)]
+            side = torch.cuda.Stream(device=image1.device)
+            side.wait_stream(torch.cuda.current_stream())
+            with torch.cuda.stream(side):
+                for _ in range(2):
+                    self._encode_impl(st[0], st[1], iters, at)
+            torch.cuda.current_stream().wait_stream(side)
+            torch.cuda.synchronize(image1.device)
+            g = torch.cuda.CUDAGraph(keep_graph=True)
+            with torch.cuda.graph(g):
+                out = self._encode_impl(st[0], st[1], iters, at)
+            self.__dict__["_graph_memsets"] = ops.graph_replace_memsets(g)
+            g.instantiate()
+            ent = (g, st, out)
+        graphs[key] = ent
+        g, st, out = ent
+        st[0].copy_(image1)
+        st[1].copy_(image2)
+        g.replay()
+        cl = lambda t: None if t is None else t.clone()  # noqa: E731
+        return {"disp": [cl(t) for t in out["disp"]], "net": [cl(t) for t in out["net"]], "stems": tuple(cl(t) for t in out["stems"])}
+
     # ---- reference API -------------------------------------------------------------------------
     def upsample_disp(self, disp, hidden_layer, stem_4x, stem_2x, stem_1x, hr_coord=None, scale=1):
         """[B,1,h,w] disparity at 1/4 res -> [B,1,Q] at the query coordinates
@@ -331,7 +407,9 @@ class ContinuousStereoBase(nn.Module):
     # ... and with it the bilinear resize of its result to 1/8 resolution (gru08's third source), instead of in front of gru08
     early_interp16 = os.environ.get("ANYSTEREO_EARLY_INTERP16", "1") != "0"
 
-    def _iterate_pipelined(self, lookup_fn, net, inp, disp, coords, iters):
+    def _iterate_pipelined(self, lookup_fn, net, inp, disp, coords, iters, keep=None):
+        """keep (encode only): {1-based iteration: {}} — the iteration's hidden state and disparity are copied into its entry, each on
+        the stream that produced it (main / side); None on the forward path, where nothing is added."""
         from ..nn.update import interp, pool2x
         ub = self.update_block
         dev = disp.device
@@ -385,6 +463,8 @@ class ContinuousStereoBase(nn.Module):
             mk("gru04_begin")
             net[0] = ub.gru04(net[0], *(inp[0]), mf, up, pre_zr=pre)
             mk("gru04_end")
+            if keep is not None and itr + 1 in keep:
+                keep[itr + 1]["net"] = net[0].clone()
             net[0].record_stream(side)
             twin = getattr(net[0], "_as_bs", None)  # blocked twin of the hidden state: read by the head on the side stream
             if twin is not None:
@@ -400,7 +480,12 @@ class ContinuousStereoBase(nn.Module):
                     if itr + 1 < iters:
                         mf = enc(disp)
                     mk("encoder_end")
+                if keep is not None and itr + 1 in keep:
+                    keep[itr + 1]["disp"] = disp.clone()
         main.wait_stream(side)
+        if keep is not None:
+            for ent in keep.values():  # copied on the side stream, read by the field's queries behind the join above
+                ent["disp"].record_stream(main)
         disp.record_stream(main)
         if ops._ACTIVE_STAMPS is not None:
             ops._ACTIVE_STAMPS.fine, ops._ACTIVE_STAMPS.prefix = False, ""
@@ -448,6 +533,9 @@ class ContinuousStereoBase(nn.Module):
         disp_preds = []
         disp_up = None
         ub = self.update_block
+        # encode(): the loop alone, keeping (disparity, hidden state) of the asked iterations; None on every forward() path
+        enc = self.__dict__.get("_encode_request")
+        keep = None if enc is None else enc["keep"]
         self.__dict__.pop("_qorder", None)
         if getattr(self, "liif_up", None) is not None:
             # reuse of the iteration-invariant upsampler branch (stem_2x) across this forward's iterations; a fresh cache per
@@ -457,6 +545,10 @@ class ContinuousStereoBase(nn.Module):
                 and not torch.is_grad_enabled() and getattr(ub, "parallel_encoder", False)
                 and type(self)._hot_update is ContinuousStereoBase._hot_update and self.pipelined_loop):
             liif = getattr(self, "liif_up", None)
+            if keep is not None:
+                disp = self._iterate_pipelined(lookup_fn, net_list, inp_list, disp, coords, iters, keep=keep)
+                enc["stems"] = (stem_4x, stem_2x, stem_1x)
+                return disp, None, [None]
             if liif is not None and stem_2x is not None and stem_1x is None and hasattr(liif, "precompute_static"):
                 # the stem_2x input of the upsampler does not change during the loop: its affinity + low-resolution first layer
                 # run on a branch of their own beside the loop instead of in front of the tail kernel after it
@@ -489,6 +581,10 @@ class ContinuousStereoBase(nn.Module):
             net_list, delta = self._hot_update(net_list, inp_list, geo_feat, disp, iter16=a.n_gru_layers == 3,
                                                iter08=a.n_gru_layers >= 2)
             disp = disp + delta
+            if keep is not None:
+                if itr + 1 in keep:
+                    keep[itr + 1].update(net=net_list[0].clone(), disp=disp.clone())
+                continue
             if test_mode and itr < iters - 1:
                 continue
             if batch_up:
@@ -501,4 +597,6 @@ class ContinuousStereoBase(nn.Module):
             disp_up = disp_preds[-1]
         if getattr(self, "liif_up", None) is not None:
             self.liif_up.__dict__.pop("_train_static", None)
+        if keep is not None:
+            enc["stems"] = (stem_4x, stem_2x, stem_1x)
         return disp, disp_up, disp_preds

@@ -558,7 +558,20 @@ class liif_out_multi_scale_Training(nn.Module):
         # second chain wait for the first: the two ran back to back, 168 us instead of ~125)
         fork = main.record_event() if side is not None else None
         early = self.__dict__.get("_early_static")  # the loop-invariant input's rows, computed beside the GRU loop
+        # a StereoField's row cache (models/field.py), {input: {"src", "pack", "u", "done"}}: an input whose tensors and pack are
+        # the cached ones reuses its rows, any other input's rows are stored.  None on the forward path.
+        rows = self.__dict__.get("_field_rows")
         for i, (parts, c, pk) in enumerate(prep):
+            ent = None if rows is None else rows.get(i)
+            if (ent is not None and ent["pack"] is pk and len(ent["src"]) == len(feats_parts[i])
+                    and all(a is b_ for a, b_ in zip(ent["src"], feats_parts[i]))):
+                main.wait_event(ent["done"])
+                ent["u"].record_stream(main)
+                us.append(ent["u"])
+                sizes.append(tuple(parts[0].shape[2:]))
+                rel_cols.append(off + c)
+                off += c + 2
+                continue
             if (early is not None and i == early["slot"] and len(parts) == len(early["parts"])
                     and all(a is b_ for a, b_ in zip(early["src"], feats_parts[i])) and early["pack"] is pk):
                 main.wait_event(early["done"])
@@ -576,6 +589,10 @@ class liif_out_multi_scale_Training(nn.Module):
                 with scope("structure_feature"):
                     aff = ops.liif_affinity(parts)
                 us.append(self._input_rows(i, parts, aff, pk))
+                if rows is not None:
+                    done = torch.cuda.Event()
+                    done.record()
+                    rows[i] = {"src": list(feats_parts[i]), "pack": pk, "u": us[-1], "done": done}
             if on_side:
                 for t_ in parts:
                     t_.record_stream(side)

@@ -597,6 +597,35 @@ def query_grid(plan, batch: int, device) -> torch.Tensor:
     return out
 
 
+def resize_disparity(src: torch.Tensor, crop, size, mul: float = 1.0, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The interpolation baseline's resize (evaluation.py:125-146, `multi_evaothers`): src fp32 [N,Hs,Ws] (or [N,1,Hs,Ws]), crop =
+    (top, left, hc, wc), size = (H, W) -> fp32 [N,H,W] = bicubic(src[:, top:top+hc, left:left+wc] * mul), one launch
+    (as_resize_disp): the unpad, the `* scale_test` and F.interpolate(mode='bicubic', align_corners=False) of the reference, with the
+    taps clamped to the crop.  A crop of the output's shape is copied (times mul).  Nothing but the output is allocated, and not
+    even that with `out` (fp32 [N,H,W], written in full)."""
+    _req(src, "resize_disparity: src")
+    if src.dim() == 4 and src.shape[1] == 1:
+        src = src[:, 0]
+    if src.dim() != 3 or src.numel() == 0:
+        raise RuntimeError(f"resize_disparity: src must be a non-empty [N,Hs,Ws] or [N,1,Hs,Ws] tensor, got {tuple(src.shape)}")
+    top, left, hc, wc = (int(v) for v in crop)
+    h, w = (int(v) for v in size)
+    n, hs, ws = src.shape
+    if hc < 1 or wc < 1:
+        raise RuntimeError(f"resize_disparity: empty crop {hc}x{wc}")
+    if top < 0 or left < 0 or top + hc > hs or left + wc > ws:
+        raise RuntimeError(f"resize_disparity: the crop (top {top}, left {left}, {hc}x{wc}) leaves the {hs}x{ws} source")
+    if h < 1 or w < 1:
+        raise RuntimeError(f"resize_disparity: empty output {h}x{w}")
+    if out is None:
+        out = torch.empty((n, h, w), device=src.device, dtype=torch.float32)
+    elif _req(out, "resize_disparity: out").device != src.device or tuple(out.shape) != (n, h, w):
+        raise RuntimeError(f"resize_disparity: out must be a {(n, h, w)} tensor on {src.device}, got {tuple(out.shape)} on {out.device}")
+    with _guard(src.device):
+        L.check(L.load().as_resize_disp(_p(src), _p(out), n, hs, ws, top, left, hc, wc, h, w, float(mul), _stream()), "resize_disp")
+    return out
+
+
 # ------------------------------------------------------------------------------------------------
 # multi-scale training batches: queries, gathered ground truth and the 1/4-resolution target (csrc/train_batch.hip)
 # ------------------------------------------------------------------------------------------------

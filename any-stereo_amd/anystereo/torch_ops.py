@@ -20,6 +20,7 @@ Stateless operators (reference call site):
     prepare_pair(image1, image2, scale, divis_by, fixed) -> (Tensor, Tensor)  evaluation.py:67-89, evaluation_validate.py:92-106, utils.py:7-26
     query_grid(image, scale, divis_by, fixed) -> Tensor                  the same lines -> hr_coord fp32 [B,Q,2] of the pair `image` [B,3,H,W]
                                                                          belongs to (its shape and device are read, not its values)
+    resize_disparity(src, crop, size, mul) -> Tensor                     evaluation.py:125-146 (unpad, * scale_test, bicubic) -> fp32 [N,H,W]
     disparity_images(disp, gt?, max_disp, color, error?, enc16, abs_thres, rel_thres) -> (Tensor?, Tensor?, Tensor?)
                                                                          evaluation.py:35-65 + save_image, visualization.py:30-55 ->
                                                                          uint8 color [B,H,W,3], error [B,H,W,3], enc16 [B,H,W,2]
@@ -55,6 +56,7 @@ _lib.define("disparity_metrics(Tensor est, Tensor gt, Tensor? valid, Tensor? noc
 _lib.define("lr_consistency(Tensor dl, Tensor dr, float thr) -> Tensor")
 _lib.define("prepare_pair(Tensor image1, Tensor image2, float scale, int divis_by, bool fixed) -> (Tensor, Tensor)")
 _lib.define("query_grid(Tensor image, float scale, int divis_by, bool fixed) -> Tensor")
+_lib.define("resize_disparity(Tensor src, int[] crop, int[] size, float mul) -> Tensor")
 _lib.define("disparity_images(Tensor disp, Tensor? gt, float max_disp, bool color, bool? error, bool enc16, float abs_thres, "
             "float rel_thres) -> (Tensor?, Tensor?, Tensor?)")
 _lib.define("motion_encoder(Tensor disp, Tensor corr, Tensor[] weights, Tensor[] biases) -> Tensor")
@@ -64,7 +66,7 @@ _lib.define("liif_upsample(Tensor[] feats, Tensor coord, Tensor[] weights, Tenso
 
 OPS = ("corr_build_pyramid", "geo_pyramid", "geo_corr_lookup", "gwc_volume", "disparity_regression", "structure_feature",
        "convex_upsample", "corr_sampler_forward", "corr_sampler_backward", "motion_encoder", "convgru_step", "disp_head",
-       "liif_upsample", "disparity_metrics", "lr_consistency", "prepare_pair", "query_grid", "disparity_images")
+       "liif_upsample", "disparity_metrics", "lr_consistency", "prepare_pair", "query_grid", "disparity_images", "resize_disparity")
 
 
 def _f(t: torch.Tensor) -> torch.Tensor:
@@ -156,6 +158,10 @@ def _query_grid(image, scale, divis_by, fixed):
     return ops.query_grid(_plan(image.shape[-2], image.shape[-1], scale, divis_by, fixed), image.shape[0], image.device)
 
 
+def _resize_disparity(src, crop, size, mul):
+    return ops.resize_disparity(src, tuple(crop), tuple(size), mul)
+
+
 def _disparity_images(disp, gt, max_disp, color, error, enc16, abs_thres, rel_thres):
     return ops.disparity_images(disp, gt, max_disp, color, error, enc16, abs_thres, rel_thres)
 
@@ -243,7 +249,7 @@ _IMPLS = {
     "corr_sampler_backward": _corr_sampler_backward, "motion_encoder": _motion_encoder, "convgru_step": _convgru_step,
     "disp_head": _disp_head, "liif_upsample": _liif_upsample,
     "disparity_metrics": _disparity_metrics, "lr_consistency": _lr_consistency, "prepare_pair": _prepare_pair,
-    "query_grid": _query_grid, "disparity_images": _disparity_images,
+    "query_grid": _query_grid, "disparity_images": _disparity_images, "resize_disparity": _resize_disparity,
 }
 for _name, _fn in _IMPLS.items():
     _lib.impl(_name, _fn, "CUDA")

@@ -21,6 +21,7 @@
 // Every operation of the coordinate arithmetic is rounded on its own, as the torch ops it restates are: no FMA contraction in
 // this file.
 #include "common.h"
+#include "cubic.h"
 
 #pragma clang fp contract(off)
 
@@ -31,24 +32,7 @@ constexpr int kThreads = 256;
 // ---- as_prepare_pair ----
 constexpr int kTileX = 64;
 constexpr int kTileY = kThreads / kTileX;
-constexpr float kA = -0.75f;
-
-__device__ __forceinline__ float cubic1(float x) { return ((kA + 2.f) * x - (kA + 3.f)) * x * x + 1.f; }
-__device__ __forceinline__ float cubic2(float x) { return ((kA * x - 5.f * kA) * x + 8.f * kA) * x - 4.f * kA; }
-
-// taps and weights of one axis for the resized index d
-__device__ __forceinline__ void cubic_axis(int d, float scale, int n_in, int idx[4], float w[4]) {
-  const float src = scale * ((float)d + 0.5f) - 0.5f;
-  const float fl = floorf(src);
-  const float t = src - fl;
-  const int i = (int)fl;
-#pragma unroll
-  for (int k = 0; k < 4; ++k) idx[k] = min(max(i - 1 + k, 0), n_in - 1);
-  w[0] = cubic2(t + 1.f);
-  w[1] = cubic1(t);
-  w[2] = cubic1(1.f - t);
-  w[3] = cubic2(2.f - t);
-}
+using as::cubic_axis;  // taps and weights of one axis (cubic.h, shared with resize_disp.hip)
 
 template <typename T, bool kResize>
 __global__ __launch_bounds__(kThreads) void prepare_pair_kernel(const T* __restrict__ in1, const T* __restrict__ in2,

@@ -698,6 +698,22 @@ int as_query_grid(float* hr_coord, int B, int h_hr, int w_hr, int p_top, int p_b
                   void* stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The interpolation baseline of arbitrary-scale evaluation (csrc/resize_disp.hip)
+ *
+ * as_resize_disp   replaces `padder.unpad(flow_pr).cpu()` followed by F.interpolate(flow_pr * scale_test, (H, W), mode='bicubic',
+ *                  align_corners=False) of the `multi_evaothers` branch (evaluation.py:125-146, with pad_for_muti_other :91-100):
+ *                  out[n, y, x] = bicubic over (src[n, top : top + hc, left : left + wc] * mul), src fp32 [N, Hs, Ws], out fp32
+ *                  [N, H, W] written in full, all N maps in one launch with 64-bit offsets.  Every tap is multiplied by `mul` first
+ *                  (one rounding), then upsample_bicubic2d as in as_prepare_pair (the same weights and summation order,
+ *                  csrc/cubic.h; no FMA contraction).  Taps are clamped to the CROP, not to the source frame: the reference un-pads
+ *                  before it interpolates.  (hc, wc) == (H, W): the copy of crop * mul — with mul == 1 the crop's bits.
+ *                  Nothing is allocated; the launch goes to `stream` and can be captured.
+ * AS_ERR_BAD_ARG: a NULL pointer, a non-positive N / Hs / Ws / H / W.  AS_ERR_BAD_SHAPE: an empty crop, a crop that leaves the
+ * source, N > 65535, H > 262140.  Checked before any device call. */
+int as_resize_disp(const float* src, float* out, int N, int Hs, int Ws, int top, int left, int hc, int wc, int H, int W, float mul,
+                   void* stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Evaluation pictures on the device (csrc/eval_images.hip)
  *
  * as_disp_images   replaces, per image of every validate_* loop, the `.cpu()` of the full-resolution prediction followed by

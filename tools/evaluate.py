@@ -10,6 +10,10 @@ has disparity k everywhere, so the right view's ground truth is k as well.  One 
     python tools/evaluate.py --pairs 2 --lsp-window 5               # the upsampler built with a 5x5 affinity window (3, 5 or 7)
     python tools/evaluate.py --pairs 2 --save-images out/           # disp_{i}.png (colour map) and error_{i}.png per pair; --enc16 adds
                                                                     # the 16-bit disp16_{i}.png, --image-limit N stops after N pairs
+    python tools/evaluate.py --pairs 4 --iters 32 --curve 4,8,16,32 # accuracy per GRU iteration from ONE loop per pair (model.encode +
+                                                                    # one field query per entry); the metrics become lists in that order
+    python tools/evaluate.py --pairs 4 --baseline bicubic           # plus the reference's interpolation baseline (multi_evaothers): this
+                                                                    # model's own scale-1 output, un-padded, times scale, bicubic resize
 
 The weights are the deterministic fill, so EPE here says nothing about a trained model: the
 line shows that the protocol runs on the device, what it counts and how fast.  No dataset readers.
@@ -62,7 +66,19 @@ def parse_args(argv=None):
                          "ranks each writes into DIR/rank<r>")
     ap.add_argument("--image-limit", type=int, default=None, help="stop writing pictures after this many pairs (per rank)")
     ap.add_argument("--enc16", action="store_true", help="with --save-images: also the 16-bit disparity PNG (disparity * 256)")
-    return ap.parse_args(argv)
+    ap.add_argument("--curve", default=None, metavar="K1,K2,...",
+                    help="evaluate these GRU iterations (1-based, ascending, each at most --iters) from one encoded pass per pair")
+    ap.add_argument("--baseline", default=None, choices=["bicubic"],
+                    help="also evaluate the interpolation baseline: the scale-1 query of the same pass resized bicubically")
+    a = ap.parse_args(argv)
+    if a.curve is not None:
+        try:
+            a.curve = tuple(int(k) for k in a.curve.split(","))
+        except ValueError:
+            ap.error(f"--curve takes comma-separated integers, got {a.curve!r}")
+        if any(k < 1 or k > a.iters for k in a.curve) or list(a.curve) != sorted(set(a.curve)):
+            ap.error(f"--curve {a.curve}: ascending distinct GRU iterations in [1, --iters = {a.iters}] expected")
+    return a
 
 
 def main():
@@ -102,13 +118,13 @@ def main():
 
     divis_by = 32 if "IGEV" in a.model else 16
     evaluate(model, list(pairs())[:1], scale=a.scale, iters=a.iters, protocol=a.protocol, divis_by=divis_by,
-             prep=a.prep)  # warm-up, not counted
+             prep=a.prep, curve=a.curve, baseline=a.baseline)  # warm-up, not counted
     ev = Evaluator(a.protocol, max_disp=a.max_disp)
     sink = None
     if a.save_images:
         sink = ImageSink(a.save_images if world == 1 else os.path.join(a.save_images, f"rank{rank}"), enc16=a.enc16, limit=a.image_limit)
     res = evaluate(model, pairs(), scale=a.scale, iters=a.iters, protocol=a.protocol, evaluator=ev, divis_by=divis_by, prep=a.prep,
-                   images=sink)
+                   images=sink, curve=a.curve, baseline=a.baseline)
     local_rate, local_pairs = res["pairs_per_s"], res["pairs"]
     written = [0.0] * world
     written[rank] = float(res.get("images_written", 0))
@@ -121,6 +137,8 @@ def main():
         written = dist.sum_over_ranks(written)
     else:
         merged, rates = {k: res[k] for k in ("all", "noc", "occ", "images")}, [local_rate]
+    if "estimates" in res:
+        merged["estimates"] = res["estimates"]
     dist.finalize()
     if rank == 0:
         print(json.dumps({"tool": "evaluate", "model": a.model, "protocol": a.protocol, "n_gpus": world, "pairs": a.pairs,
