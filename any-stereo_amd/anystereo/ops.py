@@ -885,6 +885,18 @@ class BS8:
         return v.permute(0, 1, 4, 2, 3).reshape(b, c8 * 8, h, w)[:, :self.c].contiguous()
 
 
+def _conv_workspace(d: "L.ConvDesc", dev=None) -> Optional[torch.Tensor]:
+    """Gives the descriptor of a split-precision stride-1 convolution (B, Cout, H, W set) its split-K scratch: as_conv_ws_elems
+    floats, nothing on a map too big to split.  dev: allocated there (caching allocator: no sync) and returned — the caller
+    holds it across the launch; None: a fake pointer, for the planner alone, which never dereferences it."""
+    n_ws = L.load().as_conv_ws_elems(d.B, d.Cout, d.H, d.W)
+    if n_ws <= 0:
+        return None
+    ws = None if dev is None else torch.empty(n_ws, device=dev, dtype=torch.float32)
+    d.ws, d.ws_elems = (1 << 20) if ws is None else ws.data_ptr(), n_ws
+    return ws
+
+
 def conv_plan(desc_or_args, knobs: Optional[dict] = None) -> dict:
     """What as_conv2d would launch (as_conv2d_plan): the kernel's template tuple, grid, block, LDS, K split, tiling, dual mode.
     desc_or_args: an L.ConvDesc, or the dict of a single-source convolution as conv2d would describe it: B, H, W, Cin, Cout and
@@ -909,8 +921,7 @@ def conv_plan(desc_or_args, knobs: Optional[dict] = None) -> dict:
         if a.get("dual"):
             d.dual, d.src2, d.wpack2, d.src2_bs = 1, fake, fake, d.src_bs[0]
         if a.get("ws", True) and d.precision == 1 and d.stride == 1:
-            d.ws_elems = lib.as_conv_ws_elems(d.B, d.Cout, d.H, d.W)
-            d.ws = fake if d.ws_elems > 0 else 0
+            _conv_workspace(d)
     k = None
     if knobs is not None:
         k = L.ConvKnobs(lean=1, xcd=2, xcd_stagger=0, lean_offset=0, ksplit_max=8, dma=1, wide=1, wide64=1, small_dma=1, prefer64=0)
@@ -1084,12 +1095,7 @@ def conv2d(srcs: Sequence[torch.Tensor], pack: PackedConv, act: int = L.ACT_NONE
     d.stride = stride
     d.act, d.epilogue = act, epilogue
     d.precision = 1 if pack.split else 0
-    ws = None
-    if pack.split and stride == 1:
-        n_ws = L.load().as_conv_ws_elems(b, cout, hh, ww)
-        if n_ws > 0:  # small feature map: give the kernel split-K scratch (caching allocator: no sync)
-            ws = torch.empty(n_ws, device=dev, dtype=torch.float32)
-            d.ws, d.ws_elems = ws.data_ptr(), n_ws
+    ws = _conv_workspace(d, dev) if pack.split and stride == 1 else None  # noqa: F841 (alive across the launch)
     with _guard(dev):
         L.check(L.load().as_conv2d(C.byref(d), _stream()), "conv2d")
     if dual is not None and (dual.get("out") is not None or dual.get("out_bs") is not None):
@@ -1114,12 +1120,7 @@ def conv2d_plain(x: torch.Tensor, pack: "PackedConv", act: int = L.ACT_NONE) -> 
     d.out, d.out_ctot = out.data_ptr(), cout
     d.B, d.H, d.W, d.Cin, d.Cout, d.KS = b, hh, ww, cin, cout, pack.ks
     d.stride, d.act, d.epilogue, d.precision = 1, act, L.EPI_LINEAR, 1 if pack.split else 0
-    ws = None
-    if pack.split:
-        n_ws = lib.as_conv_ws_elems(b, cout, hh, ww)
-        if n_ws > 0:
-            ws = torch.empty(n_ws, device=x.device, dtype=torch.float32)
-            d.ws, d.ws_elems = ws.data_ptr(), n_ws
+    ws = _conv_workspace(d, x.device) if pack.split else None  # noqa: F841 (alive across the launch)
     with _guard(x.device):
         L.check(lib.as_conv2d(C.byref(d), _stream()), "conv2d")
     return out
@@ -1184,9 +1185,8 @@ def conv1x1(srcs: Sequence[torch.Tensor], pack: PackedConv, act: int = L.ACT_NON
     d.B, d.H, d.W, d.Cin, d.Cout, d.KS = b, hh, ww, cin, cout, pack.ks
     d.stride, d.act, d.epilogue, d.precision = 1, act, L.EPI_LINEAR, 1 if pack.split else 0
     # the planner's view of the call conv2d would make: it hands as_conv2d split-K scratch on small maps (never dereferenced here)
-    n_ws = lib.as_conv_ws_elems(b, cout, hh, ww) if pack.split else 0
-    if n_ws > 0:
-        d.ws, d.ws_elems = 1 << 20, n_ws
+    if pack.split:
+        _conv_workspace(d)
     d.out, d.out_ctot = (1 << 20) if out is None else out.data_ptr(), cout if out is None else out.shape[1]
     d.out_coff = out_coff
     if not lib.as_conv1x1_stream_ok(C.byref(d)):

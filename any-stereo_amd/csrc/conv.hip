@@ -22,7 +22,10 @@
 // whichever source tensor owns them.
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
+#include "conv_plan.h"
 #include "split.h"
 
 namespace {
@@ -83,16 +86,14 @@ struct ConvParams {
   int lean_offset;  // conv_split_kernel<LEAN>: start delay of the grid's second half in units of 64 clocks (AS_CONV_LEAN_OFFSET)
 };
 
-constexpr int kNumCU = 256;   // MI355X
-constexpr int kEpiPartial = 3;  // internal: store the raw partial sums of a K slice into p.ws
+// conv_plan.h: kNumCU, kEpiPartial (store the raw partial sums of a K slice into p.ws), kBM x kBN (pixels x output channels of a
+// conv_igemm_kernel block), kSplitKC
 constexpr int kEpiTaps = AS_EPI_RELU_TAPS;
 
 template <int KS> struct ConvCfg;
 template <> struct ConvCfg<3> { static constexpr int KC = 8; };
 template <> struct ConvCfg<1> { static constexpr int KC = 32; };
-
-constexpr int kBM = 64;  // pixels per block
-constexpr int kBN = 64;  // output channels per block
+static_assert(ConvCfg<3>::KC == conv_kc(3) && ConvCfg<1>::KC == conv_kc(1), "conv_igemm_kernel's K chunk is the planner's");
 
 // ---- epilogue of one 32(co) x 32(pixel) accumulator tile -----------------------------------------
 // All global operands of the tile (context term, h, z) are fetched up front through raw buffer
@@ -911,7 +912,6 @@ __global__ __launch_bounds__(256) void interp_bs_kernel(const float* __restrict_
 // the halo patch double-buffered per chunk; next unit/chunk is fetched into registers under the MFMAs.
 // ================================================================================================
 
-constexpr int kSplitKC = 16;
 // cache policy bits of the staged epilogue's result stores (buffer-store aux: 1 = sc0, 2 = nt, 16 = sc1).  0 = write-back: the
 // results stay dirty in the XCD's L2 and are written out at the kernel boundary.  A/B builds only (tools/conv_variant.sh).
 #ifndef AS_EPI_STORE_AUX
@@ -1798,122 +1798,140 @@ __global__ __launch_bounds__(256) void conv_finish_kernel(ConvParams p) {
   }
 }
 
-template <int KS, int TW, int BN, int EPI, int NSUB = 1, int S = 1, bool FAST = false, bool LEAN = false>
-int launch_conv_split_epi(const ConvParams& p, hipStream_t s) {
-  if constexpr (!FAST && KS == 3 && S == 1) {  // the one-MFMA variant exists for the stride-1 3x3 convolutions (the GRU loop, the context net)
-    if (p.fast16) return launch_conv_split_epi<KS, TW, BN, EPI, NSUB, S, true>(p, s);
+// ---- host side: a validated descriptor and its plan (conv_plan.h) -> kernel arguments -> the launch table ----
+
+// The kernel arguments of a plan: copies of the descriptor and of the plan, no decision.
+ConvParams conv_fill_params(const as_conv_desc& d, const ConvPlan& pl) {
+  ConvParams p{};
+  int csum = 0;
+  for (int i = 0; i < d.n_src; ++i) {
+    p.src[i] = d.src[i];
+    p.src_c[i] = d.src_c[i];
+    p.src_end[i] = csum += d.src_c[i];
+    p.src_bs[i] = d.src_bs[i] ? 1 : 0;
   }
-  if constexpr (!LEAN && !FAST && KS == 3 && S == 1 && BN == 64) {
-    // two 4-wave blocks per CU instead of one 8-wave block when every source is blocked (AS_CONV_LEAN: 0 off, 1 = the
-    // 256-pixel blocks of the big maps, 2 = every 64-channel 3x3 launch)
-    static const int lean_mode = getenv("AS_CONV_LEAN") ? atoi(getenv("AS_CONV_LEAN")) : 1;
-    // measured (cfg 2): with >= 2 blocks for every CU the pair overlaps one block's staging / prologue / epilogue with the
-    // other's MFMAs (gru04 z|r 149.3 -> 146.6 us, head conv1 58.9 -> 54.4); with fewer blocks a CU holds ONE single-buffered
-    // block and loses (gru04 q 85.5 -> 102.8, gru08 z|r 62 -> 87), as do 128-pixel lean blocks at three per CU (156.6 vs 144.4)
-    const long long nblk = (long long)p.B * as::cdiv64((long long)p.tiles_x * p.tiles_y, NSUB) * p.n_tiles * p.ksplit;
-    // 3 (A/B knob): mode 1 + the 128-pixel blocks of the small maps (49 KB: up to three per CU, co-resident with another
-    // launch's blocks) — never the big maps' 256-block launches, which run alone and need their own double buffering
-    if (p.all_bs && (lean_mode == 2 || ((lean_mode == 1 || lean_mode == 3) && NSUB == 2 && nblk >= 2 * kNumCU) || (lean_mode == 3 && NSUB == 1)))
-      return launch_conv_split_epi<KS, TW, BN, EPI, NSUB, S, false, true>(p, s);
+  p.n_src = d.n_src;
+  p.wpack = d.wpack; p.bias = d.bias; p.add = d.add;
+  p.add_ctot = d.add_ctot; p.add_coff = d.add_coff;
+  p.h = d.h; p.z = d.z; p.out = d.out; p.out2 = d.out2;
+  if (d.epilogue == AS_EPI_LINEAR) {
+    p.out_ctot = d.out_ctot > 0 ? d.out_ctot : d.Cout;
+    p.out_coff = d.out_coff;
+  } else if (d.epilogue == AS_EPI_RELU_TAPS) {
+    p.tap_w = d.tap_w;
   }
-  constexpr int TH = 128 / TW, PATCHP = ((TH - 1) * S + KS) * ((TW - 1) * S + KS);
-  constexpr int NSC = (KS == 1) ? 4 : 1;
-  constexpr size_t wimg = (size_t)(KS * KS * NSC * 4 * BN * 16), pimg = (size_t)NSC * (4 * NSUB * PATCHP * 16);
-  // LEAN: one weight + one patch image, and room for the epilogue's staging (bias / tap weights 4 KB + the fp32 tile)
-  constexpr size_t lds_lean = (wimg + pimg > 4096 + (size_t)BN * 128 * NSUB * 4) ? wimg + pimg : 4096 + (size_t)BN * 128 * NSUB * 4;
-  constexpr size_t lds = LEAN ? lds_lean
-                              : 2 * wimg + ((KS == 3 && 2 * wimg + 2 * pimg <= 160 * 1024) ? 2 : 1) * pimg;  // the kernel's PDB rule
+  p.B = d.B; p.Cin = d.Cin; p.Cout = d.Cout; p.Cout_pad = conv_cout_pad(d.Cout); p.act = d.act;
+  p.H = pl.H; p.W = pl.W; p.Hi = pl.Hi; p.Wi = pl.Wi;
+  p.tiles_x = pl.tiles_x; p.tiles_y = pl.tiles_y; p.n_tiles = pl.n_tiles; p.chunks = pl.chunks;
+  if (d.out_bs) {
+    const int ctot = d.out_bs_ctot > 0 ? d.out_bs_ctot : (d.epilogue == AS_EPI_GRU_ZR ? d.Cout / 2 : d.Cout);
+    p.out_bs = reinterpret_cast<_Float16*>(d.out_bs);
+    p.out_bs_c8tot = (ctot + 7) / 8;
+    p.out_bs_ctot = ctot;
+    p.out_bs_coff8 = d.out_bs_coff / 8;
+    p.bs_only = d.bs_only ? 1 : 0;
+  }
+  p.all_bs = pl.all_bs;
+  if (pl.dual == kDualFused) {  // the second convolution: the upper half of the plan's channel tiles, addressed to the second problem
+    p.dual = 1;
+    p.src2 = d.src2;
+    p.src2_bs = d.src2_bs ? 1 : 0;
+    p.wpack2 = d.wpack2;
+    p.bias2 = d.bias2;
+    p.out_coff2 = d.out_coff2;
+    p.out_bs_coff8_2 = d.out_bs_coff2 / 8;
+    p.h2 = d.h2;
+    p.act2 = d.dual_act2 ? d.act2 : d.act;
+    p.dual_sep = (d.out_b || d.out_bs_b) ? 1 : 0;
+    p.out_b = d.out_b;
+    p.out_bs_b = reinterpret_cast<_Float16*>(d.out_bs_b);
+  }
+  p.xcd_map = pl.xcd_map;
+  p.fast16 = pl.FAST;
+  p.ksplit = pl.ksplit;
+  p.ws = pl.ksplit > 1 ? d.ws : nullptr;
+  p.stagger = pl.stagger;
+  p.lean_offset = pl.lean_offset;
+  return p;
+}
+
+// The launch table: the instantiations of the library (tests/golden/conv_kernels.txt), as predicates over the plan's tuple.
+constexpr bool conv_igemm_valid(int KS, int TW, int EPI) {
+  return (KS == 1 ? TW == kBM : KS == 3 && (TW == 8 || TW == 16 || TW == 32)) && EPI >= AS_EPI_LINEAR && EPI <= AS_EPI_GRU_Q;
+}
+constexpr bool conv_split_valid(int KS, int TW, int BN, int EPI, int NSUB, int S, bool FAST, bool LEAN) {
+  if (EPI < AS_EPI_LINEAR || EPI > kEpiTaps || (BN != 64 && BN != 128) || (NSUB != 1 && NSUB != 2)) return false;
+  const bool plain = NSUB == 1 && !FAST && !LEAN;
+  if (KS == 1) return TW == 128 && S == 1 && EPI != kEpiTaps && plain;
+  if (KS != 3 || (TW != 16 && TW != 32)) return false;
+  if (S == 2) return TW == 16 && BN == 64 && EPI == AS_EPI_LINEAR && plain;
+  if (S != 1) return false;
+  // 3x3, stride 1.  128-channel tiles: one sub-tile, never lean, no tap reduction; 64-channel tiles: K split over single sub-tiles only
+  if (BN == 128) return EPI != kEpiTaps && NSUB == 1 && !LEAN;
+  return !(FAST && LEAN) && !(NSUB == 2 && EPI == kEpiPartial);
+}
+
+template <int KS, int TW, int BN, int EPI, int NSUB, int S, bool FAST, bool LEAN>
+int launch_conv_split(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
+  constexpr int lds = conv_split_lds(KS, TW, BN, NSUB, S, LEAN);  // = pl.lds: the plan's tuple is this instantiation's
   static_assert(lds <= 160 * 1024, "conv_split: LDS budget");
   static_assert(!LEAN || lds <= 80 * 1024, "conv_split (lean): two blocks per CU");
   static bool configured = false;  // per instantiation; the attribute is idempotent
   if (!configured && lds > 64 * 1024) {
-    (void)hipFuncSetAttribute((const void*)conv_split_kernel<KS, TW, BN, EPI, NSUB, S, FAST, LEAN>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)conv_split_kernel<KS, TW, BN, EPI, NSUB, S, FAST, LEAN>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     configured = true;
   }
-  const long long groups = as::cdiv64((long long)p.tiles_x * p.tiles_y, NSUB);
-  const dim3 grid((unsigned)((long long)p.B * groups * p.n_tiles * p.ksplit));
-  static const int xcd_mode = getenv("AS_CONV_XCD") ? atoi(getenv("AS_CONV_XCD")) : 2;  // 0 off | 1 channel tiles together | 2 + banded pixel tiles
-  ConvParams q = p;
-  q.xcd_map = xcd_mode == 2 ? 2 : ((xcd_mode && p.n_tiles > 1) ? 1 : 0);  // 2: banded pixel tiles per XCD (any channel-tile count)
-  static const int stagger = getenv("AS_CONV_XCD_STAGGER") ? atoi(getenv("AS_CONV_XCD_STAGGER")) : 0;
-  q.stagger = stagger;
-  static const int lean_offset = getenv("AS_CONV_LEAN_OFFSET") ? atoi(getenv("AS_CONV_LEAN_OFFSET")) : 0;
-  q.lean_offset = lean_offset;
-  hipLaunchKernelGGL((conv_split_kernel<KS, TW, BN, EPI, NSUB, S, FAST, LEAN>), grid, dim3(LEAN ? 256 : 512), lds, s, q);
+  hipLaunchKernelGGL((conv_split_kernel<KS, TW, BN, EPI, NSUB, S, FAST, LEAN>), dim3((unsigned)pl.grid), dim3(pl.block), pl.lds, s, p);
   return as::check_launch("conv2d(split)");
 }
 
-template <int KS, int TW, int BN, int NSUB = 1>
-int launch_conv_split(const ConvParams& p, int epi, hipStream_t s) {
-  if (p.ksplit > 1) {
-    int rc = launch_conv_split_epi<KS, TW, BN, kEpiPartial>(p, s);
-    if (rc != AS_OK) return rc;
-    const int cwalk = (p.out_bs && epi != AS_EPI_GRU_ZR) ? (p.Cout + 7) / 8 * 8 : p.Cout;  // conv_finish_kernel's channel walk
-    const long long total = (long long)p.B * cwalk * p.H * p.W;
-    const dim3 g((unsigned)as::cdiv64(total, 256));
-    if (epi == AS_EPI_LINEAR) hipLaunchKernelGGL(conv_finish_kernel<AS_EPI_LINEAR>, g, dim3(256), 0, s, p);
-    else if (epi == AS_EPI_GRU_ZR) hipLaunchKernelGGL(conv_finish_kernel<AS_EPI_GRU_ZR>, g, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(conv_finish_kernel<AS_EPI_GRU_Q>, g, dim3(256), 0, s, p);
-    return as::check_launch("conv2d(split-K finish)");
+// conv_switch(f, Among<a, b, ...>{}, v, Among<...>{}, w, ...): f(std::integral_constant<int, v>{}, <w>{}, ...) with every run-time
+// value turned into the equal constant of its list; false, and no call, when a value is in none
+template <int... Vs> struct Among {};
+template <class F> bool conv_switch(F f) { f(); return true; }
+template <class F, int... Vs, class... Rest>
+bool conv_switch(F f, Among<Vs...>, int v, Rest... rest) {
+  return ((v == Vs && conv_switch([&](auto... cs) { f(std::integral_constant<int, Vs>{}, cs...); }, rest...)) || ...);
+}
+
+// Launches the plan's instantiation with the plan's grid, block and LDS size.  A tuple without an entry: an error, no launch.
+int conv_launch(const ConvParams& p, const ConvPlan& pl, hipStream_t s) {
+  int rc = 1;  // no entry reached
+  if (pl.family == kConvIgemm) {
+    conv_switch([&](auto ks, auto tw, auto epi) {
+      if constexpr (conv_igemm_valid(ks(), tw(), epi())) {
+        hipLaunchKernelGGL((conv_igemm_kernel<ks(), tw(), epi()>), dim3((unsigned)pl.grid), dim3(pl.block), 0, s, p);
+        rc = as::check_launch("conv2d");
+      }
+    }, Among<1, 3>{}, pl.KS, Among<8, 16, 32, 64>{}, pl.TW, Among<0, 1, 2>{}, pl.epilogue);
+  } else if (pl.family == kConvSplit) {
+    conv_switch([&](auto ks, auto tw, auto bn, auto epi, auto nsub, auto st, auto fast, auto lean) {
+      if constexpr (conv_split_valid(ks(), tw(), bn(), epi(), nsub(), st(), fast(), lean()))
+        rc = launch_conv_split<ks(), tw(), bn(), epi(), nsub(), st(), fast() != 0, lean() != 0>(p, pl, s);
+    }, Among<1, 3>{}, pl.KS, Among<16, 32, 128>{}, pl.TW, Among<64, 128>{}, pl.BN, Among<0, 1, 2, 3, 4>{}, pl.epilogue,
+       Among<1, 2>{}, pl.NSUB, Among<1, 2>{}, pl.S, Among<0, 1>{}, pl.FAST != 0, Among<0, 1>{}, pl.LEAN != 0);
   }
-  if (epi == AS_EPI_LINEAR) return launch_conv_split_epi<KS, TW, BN, AS_EPI_LINEAR, NSUB>(p, s);
-  if (epi == AS_EPI_GRU_ZR) return launch_conv_split_epi<KS, TW, BN, AS_EPI_GRU_ZR, NSUB>(p, s);
-  if (epi == AS_EPI_RELU_TAPS) {
-    if constexpr (BN == 64 && KS == 3) return launch_conv_split_epi<KS, TW, BN, kEpiTaps, NSUB>(p, s);
-    else return as::fail(AS_ERR_BAD_ARG, "conv2d(RELU_TAPS): 3x3, 64-channel tiles only");
-  }
-  return launch_conv_split_epi<KS, TW, BN, AS_EPI_GRU_Q, NSUB>(p, s);
+  return rc <= 0 ? rc : conv_no_kernel(pl);
 }
 
-template <int KS, int TW>
-int launch_conv(const ConvParams& p, int epi, hipStream_t s) {
-  const dim3 grid((unsigned)((long long)p.B * p.tiles_x * p.tiles_y * p.n_tiles));
-  if (epi == AS_EPI_LINEAR) hipLaunchKernelGGL((conv_igemm_kernel<KS, TW, AS_EPI_LINEAR>), grid, dim3(256), 0, s, p);
-  else if (epi == AS_EPI_GRU_ZR) hipLaunchKernelGGL((conv_igemm_kernel<KS, TW, AS_EPI_GRU_ZR>), grid, dim3(256), 0, s, p);
-  else hipLaunchKernelGGL((conv_igemm_kernel<KS, TW, AS_EPI_GRU_Q>), grid, dim3(256), 0, s, p);
-  return as::check_launch("conv2d");
-}
-
-int conv_kc(int KS) { return KS == 3 ? ConvCfg<3>::KC : ConvCfg<1>::KC; }
-
-// Small feature maps give too few blocks to pull the weight stream (each CU fills its LDS at ~35 GB/s, so
-// a 1/16-res GRU conv on 36 CUs is bound by 36 x that): split K over more blocks when a workspace is given.
-void conv_pick_ksplit(ConvParams& p, const as_conv_desc* d) {
-  p.ksplit = 1;
-  p.ws = nullptr;
-  if (!d->ws || d->ws_elems <= 0) return;
-  const long long blocks = (long long)p.B * p.tiles_x * p.tiles_y * p.n_tiles;
-  const long long slab = (long long)p.B * p.Cout_pad * p.H * p.W;
-  // one block per CU (the tile's LDS footprint): more blocks than CUs would just queue a second round
-  int ks = (int)(kNumCU / blocks);
-  // AS_CONV_KSPLIT_MAX (A/B knob): 1 = never split.  Alone a split launch is shorter; beside the other chain's kernels the
-  // unsplit one costs fewer CU-microseconds (no partial slabs, no finish launch) on half the CUs.
-  static const int ks_max = getenv("AS_CONV_KSPLIT_MAX") ? atoi(getenv("AS_CONV_KSPLIT_MAX")) : 8;
-  if (ks > ks_max) ks = ks_max;
-  if (ks > 8) ks = 8;
-  while (ks > 1 && (p.chunks / ks < 2 || slab * ks > d->ws_elems)) --ks;
-  if (ks > 1) { p.ksplit = ks; p.ws = d->ws; }
-}
-int conv_cout_pad(int Cout) { return ((Cout + kBN - 1) / kBN) * kBN; }
-
-// second convolution of a dual launch: twice the channel tiles, the upper half addressed to the second problem
-void conv_apply_dual(ConvParams& p, const as_conv_desc* d) {
-  p.dual = 1;
-  p.n_tiles *= 2;
-  p.src2 = d->src2;
-  p.src2_bs = d->src2_bs ? 1 : 0;
-  p.wpack2 = d->wpack2;
-  p.bias2 = d->bias2;
-  p.out_coff2 = d->out_coff2;
-  p.out_bs_coff8_2 = d->out_bs_coff2 / 8;
-  p.h2 = d->h2;
-  p.act2 = d->dual_act2 ? d->act2 : d->act;
-  p.dual_sep = (d->out_b || d->out_bs_b) ? 1 : 0;
-  p.out_b = d->out_b;
-  p.out_bs_b = reinterpret_cast<_Float16*>(d->out_bs_b);
+// One convolution: `d` has passed conv_validate and `pl` is its plan.
+int conv_run(const as_conv_desc& d, const ConvPlan& pl, hipStream_t s) {
+  const ConvParams p = conv_fill_params(d, pl);
+  const int rc = conv_launch(p, pl, s);
+  if (rc != AS_OK || !pl.finish) return rc;
+  const dim3 g((unsigned)pl.finish_grid);  // the K slices' partial sums -> the descriptor's epilogue
+  if (pl.finish_epilogue == AS_EPI_LINEAR) hipLaunchKernelGGL(conv_finish_kernel<AS_EPI_LINEAR>, g, dim3(256), 0, s, p);
+  else if (pl.finish_epilogue == AS_EPI_GRU_ZR) hipLaunchKernelGGL(conv_finish_kernel<AS_EPI_GRU_ZR>, g, dim3(256), 0, s, p);
+  else hipLaunchKernelGGL(conv_finish_kernel<AS_EPI_GRU_Q>, g, dim3(256), 0, s, p);
+  return as::check_launch("conv2d(split-K finish)");
 }
 
 }  // namespace
+
+bool as::conv_has_kernel(const as_conv_plan& pl) {
+  return pl.family == kConvIgemm ? conv_igemm_valid(pl.KS, pl.TW, pl.epilogue)
+                                 : pl.family == kConvSplit && conv_split_valid(pl.KS, pl.TW, pl.BN, pl.epilogue, pl.NSUB, pl.S, pl.FAST != 0, pl.LEAN != 0);
+}
 
 extern "C" {
 
@@ -1979,263 +1997,30 @@ int64_t as_conv_ws_elems(int B, int Cout, int H, int W) {
   if (B <= 0 || Cout <= 0 || H <= 0 || W <= 0) return 0;
   const int cpad = conv_cout_pad(Cout);
   const int bn = (cpad % 128 == 0) ? 128 : 64;
+  // Deliberately coarse and knob-free: pixel tiles counted on the flattened plane (never more than the plan's 8x16 / 4x32
+  // tiles), 128-channel tiles wherever they divide, and the cap of 8 slices whatever AS_CONV_KSPLIT_MAX says — the size depends
+  // on the problem alone, and conv_pick_ksplit fits the plan's split into whatever workspace it is given.
   const long long tiles = (long long)B * as::cdiv64((long long)H * W, 128) * (cpad / bn);
-  int ks = (int)(kNumCU / tiles);
-  if (ks > 8) ks = 8;
+  const int ks = conv_ksplit_cap(tiles, 8);
   return ks > 1 ? (int64_t)ks * B * cpad * H * W : 0;
 }
 
-int as_conv2d(const as_conv_desc* d, void* stream);
-static int conv2d_dual_sequential(const as_conv_desc* d, void* stream) {
-  as_conv_desc a = *d;
-  a.dual = 0;
-  const int rc = as_conv2d(&a, stream);
-  if (rc != AS_OK) return rc;
-  a.src[0] = d->src2; a.src_bs[0] = d->src2_bs; a.wpack = d->wpack2; a.bias = d->bias2;
-  a.out_coff = d->out_coff2; a.out_bs_coff = d->out_bs_coff2;
-  a.h = d->h2;
-  if (d->dual_act2) a.act = d->act2;
-  if (d->out_b || d->out_bs_b) {  // dense outputs of its own
-    a.out = d->out_b; a.out_ctot = d->Cout; a.out_coff = 0;
-    a.out_bs = d->out_bs_b; a.out_bs_ctot = d->Cout; a.out_bs_coff = 0;
-    a.bs_only = (d->out_b == nullptr) ? 1 : 0;
-  }
-  a.h2 = nullptr; a.out_b = nullptr; a.out_bs_b = nullptr; a.dual_act2 = 0;
-  return as_conv2d(&a, stream);
-}
-
 int as_conv2d(const as_conv_desc* d, void* stream) {
-  AS_REQUIRE(d, AS_ERR_BAD_ARG, "conv2d: null descriptor");
-  if (d->dual) {
-    AS_REQUIRE(d->n_src == 1 && d->epilogue == AS_EPI_LINEAR && !d->add && (d->stride == 0 || d->stride == 1), AS_ERR_BAD_ARG,
-               "conv2d(dual): one source, LINEAR epilogue, no add, stride 1");
-    AS_REQUIRE((d->h == nullptr) == (d->h2 == nullptr), AS_ERR_BAD_ARG, "conv2d(dual): a residual for both convolutions or for neither");
-    AS_REQUIRE(!d->dual_act2 || (d->act2 >= AS_ACT_NONE && d->act2 <= AS_ACT_LEAKY), AS_ERR_BAD_ARG, "conv2d(dual): act2=%d", d->act2);
-    AS_REQUIRE(!d->out_bs_b || (reinterpret_cast<uintptr_t>(d->out_bs_b) & 15) == 0, AS_ERR_BAD_ARG, "conv2d(dual): out_bs_b not 16-B aligned");
-    AS_REQUIRE(!(d->out_b || d->out_bs_b) || ((d->out_b != nullptr) == (d->out != nullptr && !d->bs_only) && (d->out_bs_b != nullptr) == (d->out_bs != nullptr)),
-               AS_ERR_BAD_ARG, "conv2d(dual): separate second outputs mirror the first convolution's (fp32 and / or blocked)");
-    AS_REQUIRE(d->src2 && d->wpack2 && (reinterpret_cast<uintptr_t>(d->wpack2) & 15) == 0, AS_ERR_BAD_ARG, "conv2d(dual): null / misaligned src2 / wpack2");
-    AS_REQUIRE(!d->src2_bs || (reinterpret_cast<uintptr_t>(d->src2) & 15) == 0, AS_ERR_BAD_ARG, "conv2d(dual): blocked src2 not 16-B aligned");
-    AS_REQUIRE(d->out_coff2 >= 0 && d->out_bs_coff2 >= 0 && d->out_bs_coff2 % 8 == 0, AS_ERR_BAD_SHAPE, "conv2d(dual): bad second output window");
-    if (d->precision != 1) return conv2d_dual_sequential(d, stream);
-  }
-  AS_REQUIRE(d->KS == 1 || d->KS == 3, AS_ERR_BAD_ARG, "conv2d: KS=%d (supported: 1, 3)", d->KS);
-  AS_REQUIRE(d->B > 0 && d->H > 0 && d->W > 0 && d->Cin > 0 && d->Cout > 0, AS_ERR_BAD_ARG, "conv2d: non-positive size");
-  AS_REQUIRE(d->n_src >= 1 && d->n_src <= AS_MAX_SRCS, AS_ERR_BAD_ARG, "conv2d: n_src=%d", d->n_src);
-  AS_REQUIRE(d->wpack, AS_ERR_BAD_ARG, "conv2d: null wpack");
-  const bool bs_only = d->out_bs && d->bs_only;
-  // the fp32 result may be omitted only where the blocked copy replaces it (LINEAR: out; GRU_ZR: out2)
-  AS_REQUIRE(d->out || (bs_only && d->epilogue == AS_EPI_LINEAR), AS_ERR_BAD_ARG, "conv2d: null out");
-  AS_REQUIRE((reinterpret_cast<uintptr_t>(d->wpack) & 15) == 0, AS_ERR_BAD_ARG, "conv2d: wpack not 16-B aligned");
-  ConvParams p{};
-  int csum = 0;
-  for (int i = 0; i < d->n_src; ++i) {
-    AS_REQUIRE(d->src[i] && d->src_c[i] > 0, AS_ERR_BAD_ARG, "conv2d: source %d null or empty", i);
-    p.src[i] = d->src[i];
-    p.src_c[i] = d->src_c[i];
-    csum += d->src_c[i];
-    p.src_end[i] = csum;
-    p.src_bs[i] = d->src_bs[i] ? 1 : 0;
-    AS_REQUIRE(!d->src_bs[i] || (d->precision == 1 && (d->stride == 0 || d->stride == 1)), AS_ERR_BAD_ARG,
-               "conv2d: blocked split-fp16 sources need the split-precision kernel, stride 1");
-    AS_REQUIRE(!d->src_bs[i] || (reinterpret_cast<uintptr_t>(d->src[i]) & 15) == 0, AS_ERR_BAD_ARG, "conv2d: blocked source %d not 16-B aligned", i);
-  }
-  if (d->out_bs) {
-    AS_REQUIRE(d->precision == 1 && (d->stride == 0 || d->stride == 1), AS_ERR_BAD_ARG, "conv2d: out_bs needs the split-precision kernel, stride 1");
-    AS_REQUIRE((reinterpret_cast<uintptr_t>(d->out_bs) & 15) == 0, AS_ERR_BAD_ARG, "conv2d: out_bs not 16-B aligned");
-    const int cres = d->epilogue == AS_EPI_GRU_ZR ? d->Cout / 2 : d->Cout;
-    const int ctot = d->out_bs_ctot > 0 ? d->out_bs_ctot : cres;
-    AS_REQUIRE(d->out_bs_coff >= 0 && d->out_bs_coff % 8 == 0 && d->out_bs_coff + cres <= (ctot + 7) / 8 * 8, AS_ERR_BAD_SHAPE,
-               "conv2d: out_bs channel window [%d,%d) must start at a multiple of 8 inside %d channels", d->out_bs_coff, d->out_bs_coff + cres, ctot);
-    AS_REQUIRE(d->epilogue != AS_EPI_GRU_Q || !d->bs_only, AS_ERR_BAD_ARG, "conv2d(GRU_Q): the fp32 hidden state is always written");
-    p.out_bs = reinterpret_cast<_Float16*>(d->out_bs);
-    p.out_bs_c8tot = (ctot + 7) / 8;
-    p.out_bs_ctot = ctot;
-    p.out_bs_coff8 = d->out_bs_coff / 8;
-    p.bs_only = d->bs_only ? 1 : 0;
-  }
-  AS_REQUIRE(csum == d->Cin, AS_ERR_BAD_SHAPE, "conv2d: sources hold %d channels, Cin=%d", csum, d->Cin);
-  AS_REQUIRE(d->precision == 0 || d->precision == 1, AS_ERR_BAD_ARG, "conv2d: precision=%d", d->precision);
-  const bool split = d->precision == 1;
-  const int kc_req = split ? kSplitKC : conv_kc(d->KS);
-  for (int i = 0; i + 1 < d->n_src; ++i)
-    AS_REQUIRE(d->src_c[i] % kc_req == 0, AS_ERR_BAD_SHAPE,
-               "conv2d: source %d has %d channels; every source but the last must hold a multiple of %d (concatenate first)",
-               i, d->src_c[i], kc_req);
-  p.n_src = d->n_src;
-  {
-    bool all = d->precision == 1;
-    for (int i = 0; i < d->n_src; ++i) all = all && d->src_bs[i];
-    if (d->dual) all = all && d->src2_bs;
-    static const int dma_mode = getenv("AS_CONV_DMA") ? atoi(getenv("AS_CONV_DMA")) : 1;
-    p.all_bs = (all && dma_mode) ? 1 : 0;
-  }
-  p.wpack = d->wpack; p.bias = d->bias; p.add = d->add;
-  p.add_ctot = d->add_ctot; p.add_coff = d->add_coff;
-  AS_REQUIRE(!d->add || (d->add_coff >= 0 && d->add_coff + d->Cout <= d->add_ctot), AS_ERR_BAD_SHAPE, "conv2d: add channel window [%d,%d) outside %d", d->add_coff, d->add_coff + d->Cout, d->add_ctot);
-  p.h = d->h; p.z = d->z; p.out = d->out; p.out2 = d->out2;
-  p.B = d->B; p.Cin = d->Cin; p.Cout = d->Cout; p.act = d->act;
-  p.fast16 = (d->precision == 1 && as::fast16_mode()) ? 1 : 0;
-  p.Cout_pad = conv_cout_pad(d->Cout);
-  const int epi = d->epilogue;
-  if (epi == AS_EPI_LINEAR) {
-    p.out_ctot = d->out_ctot > 0 ? d->out_ctot : d->Cout;
-    p.out_coff = d->out_coff;
-    AS_REQUIRE(bs_only || (p.out_coff >= 0 && p.out_coff + d->Cout <= p.out_ctot), AS_ERR_BAD_SHAPE, "conv2d: out channel window outside out_ctot");
-    AS_REQUIRE(!d->dual || bs_only || d->out_coff2 + d->Cout <= p.out_ctot, AS_ERR_BAD_SHAPE, "conv2d(dual): second out channel window outside out_ctot");
-    AS_REQUIRE(d->act >= AS_ACT_NONE && d->act <= AS_ACT_LEAKY, AS_ERR_BAD_ARG, "conv2d: act=%d", d->act);
-  } else if (epi == AS_EPI_GRU_ZR) {
-    AS_REQUIRE(d->h && (d->out2 || bs_only) && (d->Cout % (2 * kBN)) == 0, AS_ERR_BAD_ARG, "conv2d(GRU_ZR): needs h, out2 and Cout %% 128 == 0");
-  } else if (epi == AS_EPI_GRU_Q) {
-    AS_REQUIRE(d->h && d->z, AS_ERR_BAD_ARG, "conv2d(GRU_Q): needs h and z");
-  } else if (epi == AS_EPI_RELU_TAPS) {
-    AS_REQUIRE(d->tap_w && d->out && !d->add && !d->h && !d->out_bs && !d->dual && d->precision == 1 && d->KS == 3 && (d->stride == 0 || d->stride == 1),
-               AS_ERR_BAD_ARG, "conv2d(RELU_TAPS): needs tap_w and out; 3x3, split precision, stride 1, no add / residual / blocked copy / dual");
-    AS_REQUIRE(d->act == AS_ACT_RELU, AS_ERR_BAD_ARG, "conv2d(RELU_TAPS): act must be AS_ACT_RELU");
-    p.tap_w = d->tap_w;
-  } else {
-    return as::fail(AS_ERR_BAD_ARG, "conv2d: epilogue=%d", epi);
-  }
-  const int KC = split ? kSplitKC : conv_kc(d->KS);
-  for (int i = 0; i < d->n_src; ++i)  // 32-bit buffer offsets inside one (batch, source) tensor
-    AS_REQUIRE((long long)d->src_c[i] * d->H * d->W * 4 < 0x7FFFFFF0ll, AS_ERR_BAD_SHAPE,
-               "conv2d: source %d exceeds 2 GiB per batch element", i);
-  p.chunks = (d->Cin + KC - 1) / KC;
-  p.n_tiles = p.Cout_pad / kBN;
+  int rc = as::conv_validate(d);
+  if (rc != AS_OK) return rc;
+  const int fast16 = as::fast16_mode();
   hipStream_t s = as::as_stream(stream);
-  p.ksplit = 1;
-  p.ws = nullptr;
-  const int stride = d->stride ? d->stride : 1;  // 0 (zero-initialised descriptor) = 1
-  AS_REQUIRE(stride == 1 || (stride == 2 && split && d->KS == 3 && epi == AS_EPI_LINEAR), AS_ERR_BAD_ARG,
-             "conv2d: stride=%d (stride 2: 3x3, split precision, LINEAR epilogue only)", stride);
-  if (split) {
-    // 128-channel tiles where they tile the padded Cout.  GRU_ZR: a tile must lie inside one half of the channels (z | r: the
-    // epilogue picks its output tensor per block), so Cout / 2 has to be a multiple of the tile too — else 64-channel tiles
-    const int bn = (p.Cout_pad % 128 == 0 && !(epi == AS_EPI_GRU_ZR && d->Cout % 256 != 0)) ? 128 : 64;
-    p.n_tiles = p.Cout_pad / bn;
-    AS_REQUIRE((long long)d->H * d->W < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: plane too large");
-    p.Hi = d->H;
-    p.Wi = d->W;
-    if (stride == 2) {
-      // output plane (H-1)/2+1: 8x16 output tiles x 64 channels (the 17x33 halo patch leaves LDS room for one 64-wide weight image pair)
-      p.H = (d->H - 1) / 2 + 1;
-      p.W = (d->W - 1) / 2 + 1;
-      p.n_tiles = p.Cout_pad / 64;
-      p.tiles_x = as::cdiv(p.W, 16);
-      p.tiles_y = as::cdiv(p.H, 8);
-      AS_REQUIRE((long long)p.B * p.tiles_x * p.tiles_y * p.n_tiles < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: grid too large");
-      return launch_conv_split_epi<3, 16, 64, AS_EPI_LINEAR, 1, 2>(p, s);
-    }
-    if (d->KS == 1) {
-      p.chunks = (p.chunks + 3) / 4;  // pipeline units of four 16-channel chunks
-      p.Hi = 1;
-      p.Wi = d->H * d->W;
-      p.H = 1;
-      p.W = d->H * d->W;
-      p.tiles_x = as::cdiv(p.W, 128);
-      p.tiles_y = 1;
-      AS_REQUIRE((long long)p.B * p.tiles_x * p.n_tiles < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: grid too large");
-      conv_pick_ksplit(p, d);
-      if (d->dual) {
-        if (p.ksplit > 1) return conv2d_dual_sequential(d, stream);
-        conv_apply_dual(p, d);
-      }
-      return bn == 128 ? launch_conv_split<1, 128, 128>(p, epi, s) : launch_conv_split<1, 128, 64>(p, epi, s);
-    }
-    p.H = d->H;
-    p.W = d->W;
-    // 128-pixel tile as 8x16 or 4x32, whichever pads the image less (ties: 8x16, smaller halo)
-    const long long a16 = (long long)as::cdiv(p.W, 16) * 16 * as::cdiv(p.H, 8) * 8;
-    const long long a32 = (long long)as::cdiv(p.W, 32) * 32 * as::cdiv(p.H, 4) * 4;
-    const int tw = a32 < a16 ? 32 : 16;
-    p.tiles_x = as::cdiv(p.W, tw);
-    p.tiles_y = as::cdiv(p.H, 128 / tw);
-    AS_REQUIRE((long long)p.B * p.tiles_x * p.tiles_y * p.n_tiles < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: grid too large");
-    conv_pick_ksplit(p, d);
-    if (d->dual && p.ksplit > 1) return conv2d_dual_sequential(d, stream);
-    if (epi == AS_EPI_RELU_TAPS) {  // 64-channel tiles, whole K per block (the reduction is over a tile's channels)
-      p.ksplit = 1;
-      p.ws = nullptr;
-      p.n_tiles = p.Cout_pad / 64;
-      const long long groups2 = (long long)p.B * as::cdiv64((long long)p.tiles_x * p.tiles_y, 2) * p.n_tiles;
-      if (groups2 >= 2 * kNumCU) return tw == 16 ? launch_conv_split<3, 16, 64, 2>(p, epi, s) : launch_conv_split<3, 32, 64, 2>(p, epi, s);
-      return tw == 16 ? launch_conv_split<3, 16, 64>(p, epi, s) : launch_conv_split<3, 32, 64>(p, epi, s);
-    }
-    // big maps: 256-pixel x 64-channel blocks (two sub-tiles) pull 30 % fewer bytes per MFMA through the CU's L1
-    static const int wide_mode = getenv("AS_CONV_WIDE") ? atoi(getenv("AS_CONV_WIDE")) : 1;
-    const long long wide_blocks = (long long)p.B * as::cdiv64((long long)p.tiles_x * p.tiles_y, 2) * (p.Cout_pad / 64);
-    const long long now_blocks = (long long)p.B * p.tiles_x * p.tiles_y * p.n_tiles;
-    bool wide_ok = bn == 128 ? as::cdiv64(wide_blocks, kNumCU) <= as::cdiv64(now_blocks, kNumCU)
-                             : wide_blocks >= 2 * kNumCU;  // bn == 64: a wide block is twice the work of a current one
-    // 64-channel layers below that bar (the encoder's convc2 || convd2 dual launch: 2 x 255 narrow blocks = two rounds, or 2 x 128
-    // wide blocks = exactly one): rounds x (fixed cost + chunks x chunk time) from the block-lifetime stamps of both forms
-    // (narrow: 6.8 us prologue + park + finish, 1.2 us per chunk; wide: 10.8 us, 2.3 us per chunk; tools/conv_stamps.py)
-    static const int wide64_mode = getenv("AS_CONV_WIDE64") ? atoi(getenv("AS_CONV_WIDE64")) : 1;
-    if (!wide_ok && bn == 64 && wide64_mode) {
-      const int mult = d->dual ? 2 : 1;
-      const double t_now = (double)as::cdiv64(now_blocks * mult, kNumCU) * (6.8 + 1.2 * p.chunks);
-      const double t_wide = (double)as::cdiv64(wide_blocks * mult, kNumCU) * (10.8 + 2.3 * p.chunks);
-      wide_ok = t_wide < t_now;
-    }
-    if (wide_mode && p.ksplit == 1 && wide_ok) {
-      p.n_tiles = p.Cout_pad / 64;
-      if (d->dual) conv_apply_dual(p, d);
-      return tw == 16 ? launch_conv_split<3, 16, 64, 2>(p, epi, s) : launch_conv_split<3, 32, 64, 2>(p, epi, s);
-    }
-    // small maps with every source blocked: 64-channel tiles (two patch images fit next to their weight images -> all-DMA
-    // staging) with K split over the blocks that leaves, instead of 128-channel tiles on the register-staged path
-    static const int small_dma = getenv("AS_CONV_SMALL_DMA") ? atoi(getenv("AS_CONV_SMALL_DMA")) : 1;
-    bool use64 = bn == 64;
-    if (small_dma && p.all_bs && bn == 128 && !d->dual) {
-      p.n_tiles = p.Cout_pad / 64;
-      conv_pick_ksplit(p, d);
-      use64 = true;
-    }
-    // A/B knob AS_CONV_PREFER64=1 (off by default: measured slower on the cfg-4 step, 53.6 vs 52.8 ms): fp32 sources, 64-channel
-    // tiles when they need NO K split where the 128-channel tiles do — one fused launch instead of partial sums + a finish launch
-    static const int prefer64 = getenv("AS_CONV_PREFER64") ? atoi(getenv("AS_CONV_PREFER64")) : 0;
-    if (prefer64 && !use64 && bn == 128 && !d->dual && p.ksplit > 1) {
-      const long long blocks64 = (long long)p.B * p.tiles_x * p.tiles_y * (p.Cout_pad / 64);
-      if (blocks64 <= kNumCU) {
-        p.n_tiles = p.Cout_pad / 64;
-        p.ksplit = 1;
-        p.ws = nullptr;
-        use64 = true;
-      }
-    }
-    if (d->dual) conv_apply_dual(p, d);
-    if (tw == 16) return use64 ? launch_conv_split<3, 16, 64>(p, epi, s) : launch_conv_split<3, 16, 128>(p, epi, s);
-    return use64 ? launch_conv_split<3, 32, 64>(p, epi, s) : launch_conv_split<3, 32, 128>(p, epi, s);
-  }
-  if (d->KS == 1) {
-    // no halo: run on the flattened H*W plane
-    AS_REQUIRE((long long)d->H * d->W < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: plane too large");
-    p.H = 1;
-    p.W = d->H * d->W;
-    p.tiles_x = as::cdiv(p.W, kBM);
-    p.tiles_y = 1;
-    AS_REQUIRE((long long)p.B * p.tiles_x * p.n_tiles < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: grid too large");
-    return launch_conv<1, 64>(p, epi, s);
-  }
-  p.H = d->H;
-  p.W = d->W;
-  AS_REQUIRE((long long)d->H * d->W < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: plane too large");
-  // pick the tile shape (TH x TW = 64 pixels) that wastes the fewest pixels on this image;
-  // ties prefer 4x16 (64-B store runs, least halo) over 2x32 over 8x8
-  const int cand[3] = {16, 32, 8};
-  int best_tw = 16;
-  long long best = -1;
-  for (int i = 0; i < 3; ++i) {
-    const int tw = cand[i], th = kBM / tw;
-    const long long area = (long long)as::cdiv(p.W, tw) * tw * as::cdiv(p.H, th) * th;
-    if (best < 0 || area < best) { best = area; best_tw = tw; }
-  }
-  p.tiles_x = as::cdiv(p.W, best_tw);
-  p.tiles_y = as::cdiv(p.H, kBM / best_tw);
-  AS_REQUIRE((long long)p.B * p.tiles_x * p.tiles_y * p.n_tiles < 2147483647ll, AS_ERR_BAD_SHAPE, "conv2d: grid too large");
-  if (best_tw == 32) return launch_conv<3, 32>(p, epi, s);
-  if (best_tw == 16) return launch_conv<3, 16>(p, epi, s);
-  return launch_conv<3, 8>(p, epi, s);
+  ConvPlan pl;
+  if ((rc = conv_plan(*d, conv_knobs(), fast16, &pl)) != AS_OK) return rc;
+  if (pl.dual != kDualSequential) return conv_run(*d, pl, s);
+  // A dual launch that runs as two calls: `pl` is the first one's plan.  Both are checked and planned before the first launch.
+  as_conv_desc first = *d;
+  first.dual = 0;
+  const as_conv_desc second = as::conv_dual_second(*d);
+  ConvPlan pl2;
+  if ((rc = as::conv_validate(&second)) != AS_OK || (rc = conv_plan(second, conv_knobs(), fast16, &pl2)) != AS_OK) return rc;
+  if ((rc = conv_run(first, pl, s)) != AS_OK) return rc;
+  return conv_run(second, pl2, s);
 }
 
 int as_conv7x7_c1_relu(const float* x, const float* weight, const float* bias, float* out, int B, int H, int W,

@@ -1,11 +1,9 @@
 // The schedule of as_conv2d as a value: conv_plan() maps (descriptor, knobs) to the kernel instantiation, its grid and its
 // schedule parameters.  Pure host arithmetic — no HIP call, no data pointer dereferenced — so the whole decision runs on a
 // machine without a GPU (as_conv2d_plan in conv_plan.hip, tests/test_conv_plan_cpu.py).
-// The planner MIRRORS the dispatch: as_conv2d (conv.hip) makes the same decisions inline, with its own constants and its own
-// reading of the AS_CONV_* knobs.  Change a scheduling rule here and in conv.hip together.  What holds the two together:
-// test_conv_dispatch_runs_the_planned_kernel (GPU) compares the kernels as_conv2d really launches with the plan, one shape per
-// instantiation family; test_conv_plan_constants_are_the_dispatch_s compares the constants below with conv.hip's; the golden
-// table tests/golden/conv_plans.json pins the planner itself.
+// as_conv2d (conv.hip) is validate -> plan -> launch: conv_validate() (conv_plan.hip), conv_plan(), then the launch table keyed
+// by the plan's tuple, with the plan's grid, block and LDS size.  Every scheduling rule, every constant it needs and the one
+// reader of the AS_CONV_* knobs are in this file; tests/golden/conv_plans.json pins the plans, and the plan is what runs.
 #pragma once
 #include <stdint.h>
 #include <stdlib.h>
@@ -15,30 +13,23 @@
 #include "../../include/anystereo_hip.h"
 
 namespace as {
-int fail(int code, const char* fmt, ...);  // as in common.h (conv_plan.hip includes both: a mismatch does not compile)
-}
 
-namespace {
+int fail(int code, const char* fmt, ...);  // as in common.h (conv.hip and conv_plan.hip include both: a mismatch does not compile)
 
-using ConvKnobs = as_conv_knobs;
-using ConvPlan = as_conv_plan;
+// conv_plan.hip.  as_conv2d's argument checks, in the order a caller meets them: AS_OK, or the code with the message set
+int conv_validate(const as_conv_desc* d);
+// conv_plan.hip.  The second convolution of a dual launch as a call of its own
+as_conv_desc conv_dual_second(const as_conv_desc& d);
+// conv.hip, beside the launch table: the plan's tuple (family, KS, TW, BN, epilogue, NSUB, S, FAST, LEAN) has an entry
+bool conv_has_kernel(const as_conv_plan& pl);
 
-// the same constants as conv.hip (compared by test_conv_plan_constants_are_the_dispatch_s)
-constexpr int kNumCU = 256;     // MI355X
-constexpr int kEpiPartial = 3;  // internal epilogue: store the raw partial sums of a K slice into the workspace
-constexpr int kBM = 64;         // conv_igemm_kernel: pixels per block
-constexpr int kBN = 64;         // conv_igemm_kernel: output channels per block; the unit Cout is padded to
-constexpr int kSplitKC = 16;    // conv_split_kernel: channels per K chunk
-enum { kConvIgemm = 0, kConvSplit = 1 };
-enum { kDualNone = 0, kDualFused = 1, kDualSequential = 2 };
-
-constexpr ConvKnobs kConvKnobDefaults = {/*lean*/ 1, /*xcd*/ 2, /*xcd_stagger*/ 0, /*lean_offset*/ 0, /*ksplit_max*/ 8,
-                                         /*dma*/ 1, /*wide*/ 1, /*wide64*/ 1, /*small_dma*/ 1, /*prefer64*/ 0};
-
-// The A/B knobs of the dispatch (README: AS_CONV_*), read from the environment at first use, process-wide.
-inline const ConvKnobs& conv_knobs() {
-  static const ConvKnobs knobs = [] {
-    ConvKnobs k = kConvKnobDefaults;
+// The A/B knobs of the dispatch (README: AS_CONV_*), read from the environment at first use, process-wide.  An inline function
+// with external linkage: the translation units that include this header share ONE `knobs` object, so the library reads the
+// environment once however many of them ask.
+inline const as_conv_knobs& conv_knobs() {
+  static const as_conv_knobs knobs = [] {
+    as_conv_knobs k = {/*lean*/ 1, /*xcd*/ 2, /*xcd_stagger*/ 0, /*lean_offset*/ 0, /*ksplit_max*/ 8,
+                       /*dma*/ 1, /*wide*/ 1, /*wide64*/ 1, /*small_dma*/ 1, /*prefer64*/ 0};
     const struct { const char* name; int* v; } env[] = {
         {"AS_CONV_LEAN", &k.lean},  // 0 off | 1 the 256-pixel blocks of the big maps | 2 every 64-channel 3x3 launch | 3 = 1 + the 128-pixel blocks
         {"AS_CONV_XCD", &k.xcd},    // 0 off | 1 channel tiles together | 2 + banded pixel tiles
@@ -57,6 +48,22 @@ inline const ConvKnobs& conv_knobs() {
   }();
   return knobs;
 }
+
+}  // namespace as
+
+namespace {
+
+using ConvKnobs = as_conv_knobs;
+using ConvPlan = as_conv_plan;
+using as::conv_knobs;
+
+constexpr int kNumCU = 256;     // MI355X
+constexpr int kEpiPartial = 3;  // internal epilogue: store the raw partial sums of a K slice into the workspace
+constexpr int kBM = 64;         // conv_igemm_kernel: pixels per block
+constexpr int kBN = 64;         // conv_igemm_kernel: output channels per block; the unit Cout is padded to
+constexpr int kSplitKC = 16;    // conv_split_kernel: channels per K chunk
+enum { kConvIgemm = 0, kConvSplit = 1 };
+enum { kDualNone = 0, kDualFused = 1, kDualSequential = 2 };
 
 constexpr int conv_kc(int KS) { return KS == 3 ? 8 : 32; }  // conv_igemm_kernel: channels per K chunk (ConvCfg<KS>::KC)
 constexpr int conv_cout_pad(int Cout) { return ((Cout + kBN - 1) / kBN) * kBN; }
@@ -94,7 +101,8 @@ inline int conv_pick_ksplit(const as_conv_desc& d, const ConvKnobs& k, const Con
 
 inline int conv_plan(const as_conv_desc& d, const ConvKnobs& k, int fast16, ConvPlan* out);
 
-// A dual launch that cannot be fused runs as two calls of the same shape (conv2d_dual_sequential): the plan is the first one's.
+// A dual launch that cannot be fused runs as two calls of the same shape (the first convolution, then conv_dual_second): the
+// plan is the first one's.
 inline int conv_plan_sequential(const as_conv_desc& d, const ConvKnobs& k, int fast16, ConvPlan* out) {
   as_conv_desc first = d;
   first.dual = 0;
@@ -252,6 +260,12 @@ inline int conv_plan(const as_conv_desc& d, const ConvKnobs& k, int fast16, Conv
   pl.lds = conv_split_lds(pl.KS, pl.TW, pl.BN, pl.NSUB, pl.S, pl.LEAN != 0);
   *out = pl;
   return AS_OK;
+}
+
+// the error of a plan whose tuple the launch table does not hold (as::conv_has_kernel)
+inline int conv_no_kernel(const ConvPlan& pl) {
+  return as::fail(AS_ERR_BAD_ARG, "conv2d: no kernel of family %d with <KS %d, TW %d, BN %d, epilogue %d, NSUB %d, S %d, FAST %d, LEAN %d>",
+                  pl.family, pl.KS, pl.TW, pl.BN, pl.epilogue, pl.NSUB, pl.S, pl.FAST, pl.LEAN);
 }
 
 }  // namespace

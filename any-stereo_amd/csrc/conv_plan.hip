@@ -1,13 +1,11 @@
-// as_conv2d_plan: what as_conv2d would launch for a descriptor, without a device.  Host code only: a copy of as_conv2d's
-// argument checks (the same conditions, codes and messages, in the same order) and the planner of conv_plan.h.  as_conv2d in
-// conv.hip carries its own interleaved form of both; test_conv_plan_validates_like_conv2d compares codes and messages of the
-// two on bad descriptors, test_conv_dispatch_runs_the_planned_kernel the launched kernels with the plan.
+// The host-only half of as_conv2d: conv_validate (the argument checks: conditions, codes and messages in the order a caller
+// meets them), conv_dual_second, and as_conv2d_plan — what as_conv2d launches for a descriptor, without a device.  as_conv2d
+// (conv.hip) calls the same conv_validate and the same conv_plan (conv_plan.h), then launches the plan.
 #include "common.h"
 #include "conv_plan.h"
 
-namespace {
+namespace as {
 
-// as_conv2d's argument checks, in the order a caller meets them there
 int conv_validate(const as_conv_desc* d) {
   AS_REQUIRE(d, AS_ERR_BAD_ARG, "conv2d: null descriptor");
   as_conv_desc first;
@@ -22,7 +20,7 @@ int conv_validate(const as_conv_desc* d) {
     AS_REQUIRE(d->src2 && d->wpack2 && (reinterpret_cast<uintptr_t>(d->wpack2) & 15) == 0, AS_ERR_BAD_ARG, "conv2d(dual): null / misaligned src2 / wpack2");
     AS_REQUIRE(!d->src2_bs || (reinterpret_cast<uintptr_t>(d->src2) & 15) == 0, AS_ERR_BAD_ARG, "conv2d(dual): blocked src2 not 16-B aligned");
     AS_REQUIRE(d->out_coff2 >= 0 && d->out_bs_coff2 >= 0 && d->out_bs_coff2 % 8 == 0, AS_ERR_BAD_SHAPE, "conv2d(dual): bad second output window");
-    if (d->precision != 1) {  // runs as two calls (conv2d_dual_sequential): the remaining checks are those of the first one
+    if (d->precision != 1) {  // runs as two calls: the remaining checks are those of the first one
       first = *d;
       first.dual = 0;
       d = &first;
@@ -88,7 +86,6 @@ int conv_validate(const as_conv_desc* d) {
   return AS_OK;
 }
 
-// the second convolution of a dual launch as a call of its own
 as_conv_desc conv_dual_second(const as_conv_desc& d) {
   as_conv_desc a = d;
   a.dual = 0;
@@ -105,18 +102,19 @@ as_conv_desc conv_dual_second(const as_conv_desc& d) {
   return a;
 }
 
-}  // namespace
+}  // namespace as
 
 extern "C" {
 
 int as_conv2d_plan(const as_conv_desc* d, const as_conv_knobs* knobs, as_conv_plan* out) {
   AS_REQUIRE(out, AS_ERR_BAD_ARG, "conv2d_plan: null out");
-  int rc = conv_validate(d);
+  int rc = as::conv_validate(d);
   if (rc == AS_OK) rc = conv_plan(*d, knobs ? *knobs : conv_knobs(), as::fast16_mode(), out);
-  if (rc == AS_OK && out->dual == kDualSequential) {  // as_conv2d goes on to the second call
-    const as_conv_desc second = conv_dual_second(*d);
-    rc = conv_validate(&second);
+  if (rc == AS_OK && out->dual == kDualSequential) {  // as_conv2d checks the second call too before it launches the first
+    const as_conv_desc second = as::conv_dual_second(*d);
+    rc = as::conv_validate(&second);
   }
+  if (rc == AS_OK && !as::conv_has_kernel(*out)) rc = conv_no_kernel(*out);
   return rc;
 }
 

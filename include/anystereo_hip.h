@@ -255,7 +255,8 @@ typedef struct {
   int block, lds;     /* threads per block; dynamic LDS bytes */
   int64_t grid, finish_grid;  /* blocks */
 } as_conv_plan;
-/* The plan as_conv2d would execute for *d under *knobs (NULL: the process's knobs).  Runs as_conv2d's validation and returns its codes;
+/* The plan as_conv2d executes for *d under *knobs (NULL: the process's knobs): as_conv2d is this call followed by the launch.  Runs
+   as_conv2d's validation and returns its codes, AS_ERR_BAD_ARG too where the library holds no kernel for the planned instantiation;
    host arithmetic only: no data pointer is dereferenced, nothing is launched, no device is needed. */
 int as_conv2d_plan(const as_conv_desc* d, const as_conv_knobs* knobs, as_conv_plan* out);
 /* Streaming 1x1 convolution (pointwise.hip) for the memory-bound pointwise layers: the arithmetic of as_conv2d on the same

@@ -1,7 +1,7 @@
 """CPU (-m "not gpu"): the schedule of as_conv2d as a value.  as_conv2d_plan maps (descriptor, knobs) to the kernel instantiation,
 grid, LDS and schedule parameters without touching a device, so the whole dispatch — every knob set, in one process — is held
-row for row to tests/golden/conv_plans.json, the launches recorded from as_conv2d itself (which still decides inline: the planner
-mirrors it until as_conv2d executes the plan)."""
+row for row to tests/golden/conv_plans.json, first recorded from the launches of as_conv2d itself.  as_conv2d runs that plan:
+validate, plan, then the launch table keyed by the plan's tuple."""
 import ctypes
 import importlib.util
 import json
@@ -112,6 +112,47 @@ def test_conv_plan_validates_like_conv2d(gen):
         assert bytes(explicit) == bytes(plan)
 
 
+def test_conv_launch_table_covers_every_plan(gen, recorded, planned):
+    """as_conv2d_plan also fails when the launch table (csrc/conv.hip) has no entry for the planned tuple.  plan_table() asserts
+    that it returns 0 for each (knob set, case) it plans, and those are the rows of the golden table: every plan there has a
+    launcher."""
+    assert planned["cases"] == recorded["cases"] and list(planned["rows"]) == list(recorded["rows"])
+    assert sum(len(idx) for idx in planned["rows"].values()) == 17 * 276
+
+
+def test_conv2d_bad_descriptor_launches_nothing(gen):
+    """as_conv2d validates and plans before it launches, both halves of a dual call that runs as two calls included: a bad
+    descriptor returns its validation code and message — never AS_ERR_LAUNCH, which is what a launch gives without a device, and
+    never a launch with these fake pointers where there is one.  (The descriptors of test_conv_plan_validates_like_conv2d, and
+    two-call dual launches whose FIRST half is good and whose second is not.)"""
+    from anystereo import _lib
+    lib = _lib.load()
+
+    def bad(name, **kw):
+        d = gen.descriptor(_lib, next(c for c in gen.CASES if c["name"] == name), 0)
+        for k, v in kw.items():
+            setattr(d, k, v)
+        return d
+
+    misaligned = bad("enc_c2d2")
+    misaligned.src[0] = gen.FAKE + 4
+    g = "enc_c2d2"
+    descs = [(_lib.ConvDesc(), -1), (bad(g, KS=5), -1), (bad(g, Cin=65), -2), (bad(g, precision=2), -1), (bad(g, epilogue=1), -1),
+             (bad(g, stride=2), -1), (bad(g, out_bs_coff=4), -2), (bad(g, out_coff2=100), -2),
+             (bad(g, dual=0, epilogue=1, h=gen.FAKE, out2=gen.FAKE), -1), (bad(g, dual=0, stride=2, out_bs=0, KS=1), -1),
+             (bad(g, wpack2=0), -1), (bad(g, H=1 << 16, W=1 << 16), -2), (misaligned, -1),
+             # fp32 precision: two calls.  The second source blocked, the second output window outside the tensor
+             (bad("dual_fp32", src2_bs=1), -1), (bad("dual_fp32", out_coff2=100), -2), (bad("dual_fp32_1x1", out_coff2=65), -2)]
+    plan = _lib.ConvPlan()
+    for d, code in descs:
+        assert lib.as_conv2d(ctypes.byref(d), None) == code
+        msg = lib.as_last_error_string()
+        assert msg and lib.as_conv2d_plan(ctypes.byref(d), None, ctypes.byref(plan)) == code
+        assert lib.as_last_error_string() == msg
+    first = bad("dual_fp32", dual=0)  # the first half of those two-call launches alone is a good descriptor
+    assert lib.as_conv2d_plan(ctypes.byref(first), None, ctypes.byref(plan)) == 0
+
+
 def test_conv_plan_structs_match_header():
     """ctypes mirrors of as_conv_knobs / as_conv_plan: field order and types as in the header."""
     import re
@@ -129,12 +170,19 @@ def test_conv_plan_structs_match_header():
 
 
 def test_conv_plan_constants_are_the_dispatch_s():
-    """conv_plan.h is compiled apart from conv.hip and repeats its constants: the two texts must give them the same values."""
+    """The dispatch's constants, helpers and knob reader exist once under csrc/, in conv_plan.h; conv.hip, which includes it, holds
+    no second definition and reads no AS_CONV_* variable itself."""
     import re
     csrc = os.path.join(GOLDEN, "..", "..", "any-stereo_amd", "csrc")
-    hip, hdr = open(os.path.join(csrc, "conv.hip")).read(), open(os.path.join(csrc, "conv_plan.h")).read()
-    for name in ("kNumCU", "kEpiPartial", "kBM", "kBN", "kSplitKC"):
-        vals = [re.findall(r"constexpr int %s = (\d+);" % name, t) for t in (hip, hdr)]
-        assert len(vals[0]) == len(vals[1]) == 1 and vals[0] == vals[1], (name, vals)
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    hip, hdr = texts["conv.hip"], texts["conv_plan.h"]
+    assert 'getenv("AS_CONV_' not in hip and '#include "conv_plan.h"' in hip
+    assert [f for f, t in texts.items() if re.search(r'"AS_CONV_[A-Z0-9_]+"', t)] == ["conv_plan.h"]  # the names conv_knobs() reads
+    defs = [r"constexpr int %s\b" % n for n in ("kNumCU", "kEpiPartial", "kBM", "kBN", "kSplitKC")]
+    defs += [r"^[\w:&* ]*\b%s\(" % n for n in ("conv_cout_pad", "conv_pick_ksplit", "conv_ksplit_cap", "conv_split_lds", "conv_knobs")]
+    for pat in defs:
+        found = {f: len(re.findall(pat + r"[^;\n]*(?:=|\{)", t, flags=re.M)) for f, t in texts.items()}
+        assert {f: n for f, n in found.items() if n} == {"conv_plan.h": 1}, (pat, found)
     kc = dict(re.findall(r"template <> struct ConvCfg<(\d)> \{ static constexpr int KC = (\d+); \};", hip))
     assert kc == {"3": "8", "1": "32"} and "return KS == 3 ? 8 : 32;" in hdr
+    assert "static_assert(ConvCfg<3>::KC == conv_kc(3) && ConvCfg<1>::KC == conv_kc(1)" in hip

@@ -2480,7 +2480,7 @@ from _conv_cases import planned_kernels as _planned_kernels  # noqa: E402  (shar
 
 
 def test_conv_dispatch_runs_the_planned_kernel():
-    """as_conv2d's dispatch and the planner that mirrors it (csrc/conv_plan.h), under the default knobs, for a shape per
+    """as_conv2d launches what its planner (csrc/conv_plan.h) says, under the default knobs, for a shape per
     instantiation family: ops.conv_plan names the expected instantiation; the kernels as_conv2d really launches — their names and
     order, read from the profiler's kernel trace — are the plan's, K-split finish launches and the two calls of an unfused dual
     launch included; and the result of ops.conv2d is the fp64 convolution's (+ the epilogue in torch) within the conv parity tests'
@@ -2532,6 +2532,44 @@ def test_conv_dispatch_runs_the_planned_kernel():
     launched = sorted((e.time_range.start, m.group(0)) for e in prof.events()
                       for m in [re.search(r"conv_(split|igemm|finish)_kernel<[^>]*>", e.name)] if m)
     assert [k for _, k in launched] == [k for _, k in expected], list(zip(expected, [k for _, k in launched]))
+
+
+def test_conv_dual_as_two_calls_runs_each_half_s_plan():
+    """A dual launch that cannot be fused — fp32 precision, or split precision on a map small enough that K splits — runs as two
+    calls, each validated and planned for itself inside as_conv2d.  B 1, 3x3, 20 x 24 (4x32 tiles, partial along both axes): both
+    results are the fp64 convolutions' within the neighbouring tests' 1e-5, and the launched kernels are those of the two halves'
+    own plans, finish launches included.  In the 128 -> 128 case the halves plan differently: the first source is blocked
+    (64-channel tiles, all-DMA staging), the second is fp32 (128-channel tiles)."""
+    from torch.profiler import ProfilerActivity, profile
+
+    from _conv_cases import launched_kernels, to_bs
+
+    from anystereo import _lib as Lb, ops
+    prev = ops.get_precision()
+    b, h, w, expected = 1, 20, 24, []
+    try:
+        with profile(activities=[ProfilerActivity.CUDA]) as prof:
+            for name, prec, c, blocked in (("fp32", "fp32", 64, False), ("split", "split", 64, True), ("split_128", "split", 128, True)):
+                ops.set_precision(prec)
+                halves = [ops.conv_plan(dict(B=b, H=h, W=w, Cin=c, Cout=c, precision=int(prec == "split"), blocked=bl, act=Lb.ACT_RELU))
+                          for bl in (blocked, False)]
+                assert all((p["ksplit"] > 1) == (prec == "split") and p["dual"] == 0 for p in halves), (name, halves)
+                assert (name == "split_128") == (_planned_kernels(halves[0]) != _planned_kernels(halves[1])), (name, halves)
+                expected += [(name, k) for p in halves for k in _planned_kernels(p)]
+                x, x2 = U((b, c, h, w), 710, -2, 2), U((b, c, h, w), 711, -2, 2)
+                wt, wt2 = (U((c, c, 3, 3), 712 + i) * (3.0 / (c * 9)) ** 0.5 for i in range(2))
+                bias, bias2 = U((c,), 714) * 0.1, U((c,), 715) * 0.1
+                pk, pk2 = (ops.PackedConv().get([t.to(DEV)], [bb.to(DEV)]) for t, bb in ((wt, bias), (wt2, bias2)))
+                out = torch.full((b, 2 * c, h, w), float("nan"), device=DEV)
+                src = to_bs(x.to(DEV)) if blocked else x.to(DEV)
+                ops.conv2d([src], pk, act=Lb.ACT_RELU, out=out, dual={"src": x2.to(DEV), "pack": pk2, "out_coff": c})
+                close(out[:, :c], _ref_conv(x, wt, bias, 1).relu(), 1e-5, 1e-5, name)
+                close(out[:, c:], _ref_conv(x2, wt2, bias2, 1).relu(), 1e-5, 1e-5, name + " (second)")
+            torch.cuda.synchronize()
+    finally:
+        ops.set_precision(prev)
+    launched = launched_kernels(prof)
+    assert launched == [k for _, k in expected] and len(launched) == 2 + 4 + 4, list(zip(expected, launched))
 
 
 KNOB_SETS = [
