@@ -343,8 +343,9 @@ def to_bs(x):
     return ops.BS8(torch.stack([hi, lo], 1).view(bb, 2, cc // 8, 8, hh, ww).permute(0, 1, 2, 4, 5, 3).contiguous(), cc)
 
 
-def run_case(c, o, dev):
-    """ops.conv2d of a case.  Every output is passed in pre-filled (the caching allocator can hand back an earlier, correct result):
+def run_case(c, o, dev, put=None):
+    """ops.conv2d of a case; put(t) moves a host operand to the device (default t.to(dev); tests/_guarded.place gives it poisoned
+    neighbours).  Every output is passed in pre-filled (the caching allocator can hand back an earlier, correct result):
     out with OUT_FILL, out2 / dual outputs / blocked copies with NaN.  Returns name -> the WHOLE output tensor on the CPU (fp32;
     blocked tensors as their fp16 records), surroundings included."""
     import torch
@@ -353,17 +354,19 @@ def run_case(c, o, dev):
     B, Cout, epi = c["B"], c["Cout"], c["epi"]
     ho, wo = gen.out_plane(c)
     nan = float("nan")
+    if put is None:
+        put = lambda t: t.to(dev)  # noqa: E731
     prev = ops.get_precision()
     ops.set_precision("split" if c["prec"] else "fp32")
     try:
         with ops.fast_fp16(bool(c["fast16"])):
-            srcs = [to_bs(x.to(dev)) if ch < 0 else x.to(dev) for x, ch in zip(o["x"], c["srcs"])]
-            pk = ops.PackedConv().get([o["w"].to(dev)], [o["bias"].to(dev)])
+            srcs = [to_bs(put(x)) if ch < 0 else put(x) for x, ch in zip(o["x"], c["srcs"])]
+            pk = ops.PackedConv().get([put(o["w"])], [put(o["bias"])])
             kw, res = dict(epilogue=epi, stride=c["stride"], act=c["act"]), {}
             if "add" in o:
-                kw.update(add=o["add"].to(dev), add_coff=ADD_COFF)
+                kw.update(add=put(o["add"]), add_coff=ADD_COFF)
             if "h" in o:
-                kw["h"] = o["h"].to(dev)
+                kw["h"] = put(o["h"])
             if c["out_bs"]:
                 res["bs"] = ops.BS8.empty(B, c["out_bs"], ho, wo, dev)
                 res["bs"].t.fill_(nan)
@@ -373,11 +376,11 @@ def run_case(c, o, dev):
                 res["out"] = torch.full((B, windows * Cout + OUT_PAD, ho, wo), OUT_FILL, device=dev)
                 kw.update(out=res["out"], out_coff=OUT_COFF)
                 if c["dual"]:
-                    s2 = o["x2"].to(dev)
-                    pk2 = ops.PackedConv().get([o["w2"].to(dev)], [o["bias2"].to(dev)])
+                    s2 = put(o["x2"])
+                    pk2 = ops.PackedConv().get([put(o["w2"])], [put(o["bias2"])])
                     dual = {"src": to_bs(s2) if c["dual"] == "bs" else s2, "pack": pk2, "act": act2_of(c)}
                     if "h2" in o:
-                        dual["h"] = o["h2"].to(dev)
+                        dual["h"] = put(o["h2"])
                     if c["dual"] == "sep":
                         res["out_b"] = dual["out"] = torch.full((B, Cout, ho, wo), nan, device=dev)
                         if c["out_bs"]:
@@ -392,13 +395,13 @@ def run_case(c, o, dev):
                 kw.update(out=res["out"], out2=res["out2"])
             elif epi == Q:
                 res["out"] = torch.full((B, Cout, ho, wo), OUT_FILL, device=dev)
-                kw.update(out=res["out"], z=o["z"].to(dev))
+                kw.update(out=res["out"], z=put(o["z"]))
             else:
                 res["out"] = torch.full((B, (Cout + 63) // 64 * 9, ho, wo), OUT_FILL, device=dev)
-                kw.update(out=res["out"], tap_w=o["tap_w"].to(dev))
+                kw.update(out=res["out"], tap_w=put(o["tap_w"]))
             ops.conv2d(srcs, pk, **kw)
             if epi == TAPS:
-                res["tss"] = ops.tap_shift_sum(res["out"], o["head_bias"].to(dev))
+                res["tss"] = ops.tap_shift_sum(res["out"], put(o["head_bias"]))
     finally:
         ops.set_precision(prev)
     return {k: (v.t if isinstance(v, ops.BS8) else v).cpu() for k, v in res.items()}

@@ -719,6 +719,94 @@ def test_whole_model(name, golden, precision):
             assert (p.cpu() - g[f"pred_{i}"]).abs().mean().item() < 1e-3
 
 
+# ---- allocation hygiene of the whole model (tests/_guarded.py; the entry points one by one: tests/test_memory_hygiene_gpu.py) ----
+
+def _hygiene_forward(name, put, graph=False, iters=2, calls=1):
+    """A fresh model (fresh weight packs) and `calls` forward passes in test_mode at 64x128, scale 1.5."""
+    from anystereo.harness.synthetic import fill_module_deterministic, synthetic_pair
+    from anystereo.models import __models__, default_args
+    key = "continuous_IGEVStereo" if name == "igev" else "continuous_RAFTStereo"
+    model = __models__[key](default_args(key)).eval()
+    fill_module_deterministic(model, base_seed=1)
+    model = model.to(DEV)
+    img1, img2 = synthetic_pair(1, 64, 128, shift=6, seed=99)
+    img1, img2, scale = put(img1), put(img2), put(torch.tensor([[1.5]]))
+    coord = O.make_coord([96, 192]).view(1, -1, 2)
+    with torch.no_grad():
+        if graph:
+            model.enable_graph(True)
+        return [model(img1, img2, iters=iters, test_mode=True, hr_coord=put(coord), scale=scale) for _ in range(calls)]
+
+
+@pytest.mark.parametrize("name", ["igev", "raft"])
+def test_whole_model_allocation_hygiene(name, precision):
+    """The eager forward with every torch.empty buffer of ops.py and nn/*.py poisoned and guarded (NaN, then finite garbage) and the
+    inputs placed between poisoned neighbours: the guards stay intact and the output is the plain run's, bit for bit."""
+    from _guarded import PATTERNS, guarded, place
+    (plain,) = _hygiene_forward(name, lambda t: place(t, DEV))
+    assert torch.isfinite(plain).all()
+    for pattern in PATTERNS:
+        with guarded(pattern) as g:
+            (out,) = _hygiene_forward(name, lambda t: place(t, DEV))
+            g.check()
+            n, out = len(g.buffers), out.clone()
+        assert torch.isfinite(out).all(), f"fill 0x{pattern:02X}: non-finite output"
+        assert torch.equal(out, plain), f"fill 0x{pattern:02X}: {int((out != plain).sum())} of {out.numel()} output elements differ from the plain run"
+        print(f"[hygiene {name} {precision} 0x{pattern:02X}] {n} guarded buffers, guards intact, output bit-equal")
+
+
+@pytest.mark.parametrize("name", ["igev", "raft"])
+def test_whole_model_training_step_allocation_hygiene(name):
+    """The G8 step (tiny_train_case, split mode) plain and under both fills.  Finite loss and gradients, guards intact.  Held to what
+    test_training_step_is_bit_repeatable holds between two plain runs of the default mode, and to nothing wider: loss and every
+    prediction bit-equal; the backward starts with the upsampler's float-atomic scatter-adds, so no parameter gradient is held
+    bit-equal there — EVERY parameter gradient within that test's 1e-5 of its maximum."""
+    from _guarded import PATTERNS, guarded, place
+    l0, p0, g0 = _g8_run(name, "split", put=lambda t: place(t, DEV))
+    for pattern in PATTERNS:
+        with guarded(pattern) as g:
+            l1, p1, g1 = _g8_run(name, "split", put=lambda t: place(t, DEV))
+            g.check()
+            n, l1, p1, g1 = len(g.buffers), l1.clone(), [t.clone() for t in p1], {k: v.clone() for k, v in g1.items()}
+        assert torch.isfinite(l1) and sorted(g1) == sorted(g0)
+        bad = [k for k, v in g1.items() if not torch.isfinite(v).all()]
+        assert not bad, f"fill 0x{pattern:02X}: non-finite gradients {bad[:8]}"
+        assert torch.equal(l0, l1), f"fill 0x{pattern:02X}: loss {l1.item()!r} vs the plain run's {l0.item()!r}"
+        for a, b in zip(p0, p1):
+            assert torch.equal(a, b), f"fill 0x{pattern:02X}: a prediction differs from the plain run"
+        # every parameter gradient, not only the stored ones: within 1e-5 of its maximum, or — the form that test's deterministic
+        # branch uses for gradients that are zero in exact arithmetic — its maximum below 1e-6 of the largest gradient's
+        top = max(v.abs().max().item() for v in g0.values())
+        worst = 0.0
+        for k in sorted(g0):
+            d = ((g0[k] - g1[k]).abs().max() / g0[k].abs().max().clamp_min(1e-30)).item()
+            tiny = max(g0[k].abs().max().item(), g1[k].abs().max().item()) < 1e-6 * top
+            worst = worst if tiny else max(worst, d)
+            assert d < 1e-5 or tiny, f"fill 0x{pattern:02X}: {k} differs from the plain run by {d:.2e} of its maximum"
+        print(f"[hygiene train {name} 0x{pattern:02X}] {n} guarded buffers, guards intact, forward bit-equal, all {len(g0)} gradients within {worst:.1e}")
+
+
+@pytest.mark.parametrize("precision", ["fp32", "split"])
+def test_whole_model_graph_replay_allocation_hygiene(precision):
+    """The default IGEV model as in test_default_model_graph_capture_in_both_precisions (64x128, 3 iterations), captured under
+    guarded(0xFF): the poison fills are nodes of the graph and run at every replay.  Two replays bit-equal, each within that
+    test's 1e-4 of the plain eager result and finite, guards intact after the second."""
+    from anystereo import ops
+    from _guarded import NAN_FILL, guarded, place
+    prev = ops.get_precision()
+    ops.set_precision(precision)
+    try:
+        (eager,) = _hygiene_forward("igev", lambda t: place(t, DEV), iters=3)
+        with guarded(NAN_FILL) as g:
+            g1, g2 = (t.clone() for t in _hygiene_forward("igev", lambda t: place(t, DEV), graph=True, iters=3, calls=2))
+            g.check()
+        assert torch.isfinite(g1).all() and torch.isfinite(g2).all()
+        assert torch.equal(g1, g2), f"{int((g1 != g2).sum())} of {g1.numel()} elements differ between two replays"
+        assert (g1 - eager).abs().max().item() <= 1e-4
+    finally:
+        ops.set_precision(prev)
+
+
 @pytest.mark.parametrize("name", ["igev", "raft"])
 def test_model_options_vs_reference(name, golden, precision):
     """forward() branches beyond the main G7 fixture, HIP path vs the imported reference (tests/golden/model_opts.npz):
@@ -953,9 +1041,11 @@ def _g8_limits(name):
     return elem, norm
 
 
-def _g8_run(name, mode, fast16=False):
-    """The G8 step of the product model: (loss, predictions, {parameter: gradient / loss scale}, model).
-    fast16: the one-MFMA mode of the forward / dgrad convolutions (fp16 operands: the reference's autocast arithmetic)."""
+def _g8_run(name, mode, fast16=False, put=None):
+    """The G8 step of the product model: (loss, predictions, {parameter: gradient / loss scale}).
+    fast16: the one-MFMA mode of the forward / dgrad convolutions (fp16 operands: the reference's autocast arithmetic).
+    put: how a host input reaches the device (default .to(DEV); tests/_guarded.place gives it poisoned neighbours)."""
+    put = put or (lambda t: t.to(DEV))
     from anystereo import ops
     from anystereo.harness.metrics import sequence_loss_multiscale
     from anystereo.harness.synthetic import fill_module_deterministic, tiny_train_case
@@ -973,9 +1063,9 @@ def _g8_run(name, mode, fast16=False):
     try:
         ops.set_precision(mode)
         with ops.fast_fp16(bool(fast16)):
-            res = model(img1.to(DEV), img2.to(DEV), iters=3, hr_coord=coord.to(DEV), scale=scale.to(DEV))
+            res = model(put(img1), put(img2), iters=3, hr_coord=put(coord), scale=put(scale))
             preds = res[1] if name == "igev" else res
-            gtd = gt.to(DEV)
+            gtd = put(gt)
             loss, _ = sequence_loss_multiscale(preds, gtd, ((gtd < 512) & (gtd > 0)).float(), max_disp=args.max_disp)
             (loss * ls).backward()
             torch.cuda.synchronize()
