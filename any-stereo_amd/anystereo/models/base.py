@@ -17,6 +17,7 @@ import torch.nn as nn
 
 from .. import grad as G
 from .. import ops
+from ..graphs import GraphCache, GraphKey, capture_pass, tensors_fingerprint
 from ..harness.timing import scope
 from ..nn import functional as AF
 from ..nn.liif import liif_out_multi_scale_Training
@@ -85,7 +86,8 @@ class ContinuousStereoBase(nn.Module):
         """The reference's `coords` argument of the lookup (x index of every pixel, continuous_IGEVstereo.py:279): a constant of
         the shape — built once per (shape, device) OUTSIDE a capture (the forward's eager warm-up passes) and reused, so the
         replayed graph carries no arange / cast / repeat launches between the cost aggregation and the loop.  The HIP lookup
-        regenerates the grid itself (`_as_pixel_grid`); callers that substitute their own lookup read the tensor."""
+        regenerates the grid itself (`_as_pixel_grid`); callers that substitute their own lookup read the tensor, so a captured
+        pass holds the grids of its capture (`_replay_cached`) and this cache may drop them at any time."""
         cache = self.__dict__.setdefault("_pixel_grids", {})
         key = (b, h, w, str(device))
         g = cache.get(key) if os.environ.get("ANYSTEREO_GRID_CACHE", "1") != "0" else None
@@ -179,29 +181,26 @@ class ContinuousStereoBase(nn.Module):
     # launch path (PyTorch dispatch + ctypes) from the critical path.  Opt-in (`enable_graph(True)`), inference
     # only; inputs are copied into static buffers, the result is a clone.
     # A replay runs no Python: it reads the packed / BatchNorm-folded weight buffers that existed at capture time.  So a
-    # graph is keyed on (input shapes, iters, device, matrix-core mode, WEIGHTS FINGERPRINT): an optimizer step,
-    # load_state_dict(), .to() / .half() or set_precision() between two calls selects (captures) another graph instead of
-    # replaying stale weights; train() / load_state_dict() / _apply() drop every graph.  Not seen by the fingerprint:
-    # writes through `.data` (they do not bump the version counter) — call `enable_graph(True)` again after such edits.
-    # The cache is an LRU of `graph_cache_size` entries (each holds a private memory pool with a whole forward), so
-    # datasets with per-image sizes (ETH3D, Middlebury) do not grow memory without bound.
+    # graph is keyed (graphs.GraphKey) on input shapes, `at`, iters, device, matrix-core mode, WEIGHTS FINGERPRINT and the
+    # `stamps` object: an optimizer step, load_state_dict(), .to() / .half() or set_precision() between two calls selects
+    # (captures) another graph instead of replaying stale weights; train() / load_state_dict() / _apply() drop every graph.
+    # Not seen by the fingerprint: writes through `.data` (they do not bump the version counter) — call
+    # `enable_graph(True)` again after such edits.
+    # The cache (`_graphs`, shared by forward and encode) is an LRU of `graph_cache_size` entries (each holds a private memory
+    # pool with a whole forward), so datasets with per-image sizes (ETH3D, Middlebury) do not grow memory without bound.
+    # Capture, replay and the cache itself: graphs.py.
     graph_cache_size = 2
 
     def enable_graph(self, flag: bool = True):
         self._use_graph = bool(flag)
-        self._graphs = {}
+        self._graphs = GraphCache()
 
     def _weights_fingerprint(self):
-        ver = ptr = n = 0
-        for t in list(self.parameters()) + list(self.buffers()):
-            ver += t._version
-            ptr ^= t.data_ptr() + 0x9E3779B97F4A7C15 * n & 0xFFFFFFFFFFFFFFFF
-            n += 1
-        return (n, ver, ptr)
+        return tensors_fingerprint(list(self.parameters()) + list(self.buffers()))  # lists: a chain of the generators is 8 % slower
 
     def _drop_graphs(self):
         if self.__dict__.get("_graphs"):
-            self.__dict__["_graphs"] = {}
+            self._graphs.clear()
 
     def train(self, mode: bool = True):
         self._drop_graphs()
@@ -242,44 +241,27 @@ class ContinuousStereoBase(nn.Module):
         finally:
             ops.set_stamps(None)
 
-    def _forward_graphed(self, image1, image2, iters, hr_coord, scale):
-        key = (tuple(image1.shape), tuple(hr_coord.shape), tuple(scale.shape), int(iters), image1.device.index,
-               ops.get_precision(), ops.get_fast_fp16() or bool(getattr(self.args, "mixed_precision", False)),
-               self._weights_fingerprint(), id(self.__dict__.get("stamps")))
-        graphs = self.__dict__.setdefault("_graphs", {})
-        ent = graphs.pop(key, None)
+    def _graph_key(self, kind, image1, shapes, at, iters, weights):
+        return GraphKey(kind, shapes, at, int(iters), image1.device.index, ops.get_precision(),
+                        ops.get_fast_fp16() or bool(getattr(self.args, "mixed_precision", False)), weights, self.__dict__.get("stamps"))
+
+    def _replay_cached(self, key, fn, inputs):
+        """The outputs of the captured fn(*inputs) for `key` (captured now on a miss), valid until the entry's next replay."""
+        ent = self._graphs.get(key)
         if ent is None:
-            while len(graphs) >= max(1, self.graph_cache_size):  # least recently used first (dict order = recency)
-                graphs.pop(next(iter(graphs)))
-            st = [t.detach().clone() for t in (image1, image2, hr_coord, scale)]
-            side = torch.cuda.Stream(device=image1.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):  # warm-up: MIOpen solver search, weight packing, allocator
-                for _ in range(2):
-                    st[2].copy_(hr_coord)
-                    self._forward_impl_marked(st[0], st[1], iters=iters, test_mode=True, hr_coord=st[2], scale=st[3])
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize(image1.device)
-            keep = os.environ.get("ANYSTEREO_INFER_GRAPH_KEEP", "1") != "0"  # 0 (diagnostics): instantiate at capture end, no node rewrite
-            g = torch.cuda.CUDAGraph(keep_graph=True) if keep else torch.cuda.CUDAGraph()
-            st[2].copy_(hr_coord)
-            with torch.cuda.graph(g):
-                out = self._forward_impl_marked(st[0], st[1], iters=iters, test_mode=True, hr_coord=st[2], scale=st[3])
-            # memset nodes (a library zero-filling through hipMemsetAsync) are not reliably ordered inside long graphs on this ROCm
-            # stack (csrc/graph.hip): rewritten as fill kernel nodes before instantiation.  This library issues none
-            # itself; the count is kept for inspection.
-            if keep:
-                self.__dict__["_graph_memsets"] = ops.graph_replace_memsets(g)
-                g.instantiate()
-            ent = (g, st, out)
-        graphs[key] = ent  # (re-)insert as most recently used
-        g, st, out = ent
-        st[0].copy_(image1)
-        st[1].copy_(image2)
-        st[2].copy_(hr_coord)
-        st[3].copy_(scale)
-        g.replay()
-        return out.clone()
+            # the pixel grid is created in the warm-up, outside the capture, and the captured lookup is handed its address: the entry
+            # keeps it alive, whatever happens to the `_pixel_grids` cache
+            ent = capture_pass(fn, inputs, inputs[0].device, refs=lambda: tuple(self.__dict__.get("_pixel_grids", {}).values()))
+            self._graphs.put(key, ent, self.graph_cache_size)
+        return ent.replay(*inputs)
+
+    def _forward_graphed(self, image1, image2, iters, hr_coord, scale):
+        key = self._graph_key("forward", image1, (tuple(image1.shape), tuple(hr_coord.shape), tuple(scale.shape)), None, iters,
+                              self._weights_fingerprint())
+
+        def fn(i1, i2, hr, sc):
+            return self._forward_impl_marked(i1, i2, iters=iters, test_mode=True, hr_coord=hr, scale=sc)
+        return self._replay_cached(key, fn, (image1, image2, hr_coord, scale)).clone()
 
     # ---- a finished pass as a field: query it again (models/field.py) -------------------------------------------------------
     def encode(self, image1, image2, iters=32, at=None):
@@ -326,34 +308,9 @@ class ContinuousStereoBase(nn.Module):
         return {"disp": [req["keep"][k]["disp"] for k in at], "net": [req["keep"][k]["net"] for k in at], "stems": stems}
 
     def _encode_graphed(self, image1, image2, iters, at, fingerprint):
-        """`_forward_graphed` for the loop alone: the same cache, LRU rule, warm-up and memset rewrite; the key carries `at`."""
-        key = ("encode", tuple(image1.shape), tuple(at), int(iters), image1.device.index, ops.get_precision(),
-               ops.get_fast_fp16() or bool(getattr(self.args, "mixed_precision", False)), fingerprint,
-               id(self.__dict__.get("stamps")))
-        graphs = self.__dict__.setdefault("_graphs", {})
-        ent = graphs.pop(key, None)
-        if ent is None:
-            while len(graphs) >= max(1, self.graph_cache_size):
-                graphs.pop(next(iter(graphs)))
-            st = [t.detach().clone() for t in (image1, image2)]
-            side = torch.cuda.Stream(device=image1.device)
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(2):
-                    self._encode_impl(st[0], st[1], iters, at)
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize(image1.device)
-            g = torch.cuda.CUDAGraph(keep_graph=True)
-            with torch.cuda.graph(g):
-                out = self._encode_impl(st[0], st[1], iters, at)
-            self.__dict__["_graph_memsets"] = ops.graph_replace_memsets(g)
-            g.instantiate()
-            ent = (g, st, out)
-        graphs[key] = ent
-        g, st, out = ent
-        st[0].copy_(image1)
-        st[1].copy_(image2)
-        g.replay()
+        """`_forward_graphed` for the loop alone: the same cache and LRU; the key carries `at`."""
+        key = self._graph_key("encode", image1, (tuple(image1.shape),), tuple(at), iters, fingerprint)
+        out = self._replay_cached(key, lambda i1, i2: self._encode_impl(i1, i2, iters, at), (image1, image2))
         cl = lambda t: None if t is None else t.clone()  # noqa: E731
         return {"disp": [cl(t) for t in out["disp"]], "net": [cl(t) for t in out["net"]], "stems": tuple(cl(t) for t in out["stems"])}
 

@@ -81,8 +81,7 @@ class continuous_RaftStereo(ContinuousStereoBase):
             stem_1x = self.stem_1(image1) if hasattr(self, "stem_1") else None
             stem_2x = self.stem_2(image1 if stem_1x is None else stem_1x)
             stem_4x = self.stem_4(stem_2x)
-        self.__dict__["_stem_1x"] = stem_1x
-        return net_list, ctx_list, stem_2x, stem_4x
+        return net_list, ctx_list, stem_2x, stem_4x, stem_1x
 
     def _forward_impl(self, image1, image2, iters=12, flow_init=None, test_mode=False, hr_coord=None, scale=1.0, output_raw=False):
         G.begin_forward()  # deferred-gradient anchors are scoped to this forward (grad.py)
@@ -97,13 +96,13 @@ class continuous_RaftStereo(ContinuousStereoBase):
                 side = self.update_block._side_stream(image1.device)
                 side.wait_stream(main)
                 with torch.cuda.stream(side):
-                    net_list, ctx_list, stem_2x, stem_4x = self._context(image1)
+                    net_list, ctx_list, stem_2x, stem_4x, stem_1x = self._context(image1)
             match_left, match_right = self.fnet([image1, image2])
             if side is None:
-                net_list, ctx_list, stem_2x, stem_4x = self._context(image1)
+                net_list, ctx_list, stem_2x, stem_4x, stem_1x = self._context(image1)
             else:
                 main.wait_stream(side)
-                for t in net_list + ctx_list + [t for t in (stem_2x, stem_4x, self.__dict__.get("_stem_1x")) if t is not None]:
+                for t in net_list + ctx_list + [t for t in (stem_2x, stem_4x, stem_1x) if t is not None]:
                     t.record_stream(main)
         net_list = [n.float() for n in net_list]
         inp_list = [list(c.float().split(split_size=c.shape[1] // 3, dim=1)) for c in ctx_list]
@@ -113,7 +112,7 @@ class continuous_RaftStereo(ContinuousStereoBase):
         coords = self._pixel_grid(b, h, w, match_left.device)
         disp0 = match_left.new_zeros((b, 1, h, w), dtype=torch.float32)
         disp, disp_up, disp_preds = self._iterate(corr_fn, net_list, inp_list, disp0, coords, iters, test_mode,
-                                                  stem_4x, stem_2x, hr_coord, scale, stem_1x=self.__dict__.pop("_stem_1x", None))
+                                                  stem_4x, stem_2x, hr_coord, scale, stem_1x=stem_1x)
         if test_mode:
             return (disp, disp_up) if output_raw else disp_up
         return disp_preds

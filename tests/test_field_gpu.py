@@ -135,7 +135,7 @@ def test_graph_replay_equals_eager(family):
             g2 = model.encode(img1, img2, iters=ITERS, at=(2, 4))
             assert len(model._graphs) == 1
             other = model.encode(img1, img2, iters=ITERS, at=(1, 4))
-        assert len(model._graphs) == 2 and len({k[2] for k in model._graphs}) == 2  # two `at` sets, two graphs
+        assert len(model._graphs) == 2 and len({k.at for k in model._graphs}) == 2  # two `at` sets, two graphs
         assert other.at == (1, 4)
         for k in (2, 4):
             q1, q2 = g1.query(coord.clone(), scale, at=k), g2.query(coord.clone(), scale, at=k)

@@ -46,7 +46,8 @@ def main():
         with torch.no_grad():
             call = lambda: model(i1, i2, iters=wl.iters, test_mode=True, hr_coord=coord, scale=scale)  # noqa: E731
             call()
-            g, st, out = next(reversed(model._graphs.values()))
+            ent = next(reversed(model._graphs.values()))
+            g, st, out = ent.graph, ent.static, ent.out
             tag = "marked" if marked else "plain"
             res[tag + "_call_ms"] = [timed(call, a.steps) for _ in range(3)]
             res[tag + "_replay_only_ms"] = [timed(g.replay, a.steps) for _ in range(3)]

@@ -18,8 +18,7 @@ with torch.no_grad():
     for _ in range(3):
         out = model(i1, i2, iters=wl.iters, test_mode=True, hr_coord=coord.clone(), scale=sc)
     torch.cuda.synchronize()
-    ent = next(iter(model._graphs.values()))
-    g = ent[0]
+    g = next(reversed(model._graphs.values())).graph
     for label, fn in (("g.replay() alone", lambda: g.replay()),
                       ("model(...) (fingerprint + 4 input copies + replay + clone)",
                        lambda: model(i1, i2, iters=wl.iters, test_mode=True, hr_coord=coord, scale=sc)),

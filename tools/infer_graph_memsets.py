@@ -19,6 +19,6 @@ for name in ("cfg1", "cfg2", "cfg3"):
         model.enable_graph(True)
         outs = [model(*inp[:2], iters=wl.iters, test_mode=True, hr_coord=inp[2].clone(), scale=inp[3]) for _ in range(3)]
     d = max((o - eager).abs().max().item() for o in outs)
-    print(f"{name}: memset nodes (replaced, left) = {model.__dict__.get('_graph_memsets')}; max |graph - eager| over 3 replays = {d:.3e}", flush=True)
+    print(f"{name}: memset nodes (replaced, left) = {next(reversed(model._graphs.values())).memsets}; max |graph - eager| over 3 replays = {d:.3e}", flush=True)
     del model
     torch.cuda.empty_cache()
