@@ -20,3 +20,21 @@ def source_hash() -> str | None:
             h.update(open(os.path.join(CSRC, f), "rb").read())
     h.update(open(HEADER, "rb").read())
     return h.hexdigest()[:16]
+
+
+SCENES_CSRC = os.path.join(CSRC, "scenes")
+SCENES_HEADER = os.path.join(PKG, "..", "..", "include", "anystereo_scenes.h")
+
+
+def scenes_source_hash() -> str | None:
+    """The same for libanystereo_scenes.so: csrc/scenes/* and include/anystereo_scenes.h (`scn_source_hash()`).  `source_hash()` above
+    lists the top level of csrc/ only, so the scene sources are no part of the main library's hash."""
+    if not (os.path.isdir(SCENES_CSRC) and os.path.exists(SCENES_HEADER)):
+        return None
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(SCENES_CSRC)):
+        if f.endswith((".hip", ".h")):
+            h.update(f.encode())
+            h.update(open(os.path.join(SCENES_CSRC, f), "rb").read())
+    h.update(open(SCENES_HEADER, "rb").read())
+    return h.hexdigest()[:16]

@@ -1,4 +1,4 @@
-"""Build libanystereo_hip.so (gfx950 only) in-tree with hipcc.
+"""Build libanystereo_hip.so and libanystereo_scenes.so (gfx950 only) in-tree with hipcc.
 
     python any-stereo_amd/build.py [--force]
 
@@ -36,12 +36,59 @@ def _newer(src_list, target) -> bool:
     return any(os.path.getmtime(s) > t for s in src_list)
 
 
-def _source_hash() -> str:
+def _srchash():
     import importlib.util
     spec = importlib.util.spec_from_file_location("anystereo_srchash", os.path.join(HERE, "anystereo", "_srchash.py"))
     mod = importlib.util.module_from_spec(spec)
     spec.loader.exec_module(mod)
-    return mod.source_hash()
+    return mod
+
+
+def _source_hash() -> str:
+    return _srchash().source_hash()
+
+
+# libanystereo_scenes.so (include/anystereo_scenes.h): the procedural scenes' library, a build of its own — csrc/scenes/ is no part of
+# libanystereo_hip.so, its source hash or its ABI
+SCENES_CSRC = os.path.join(CSRC, "scenes")
+SCENES_OBJ = os.path.join(OBJ, "scenes")
+SCENES_LIB = os.path.join(LIBDIR, "libanystereo_scenes.so")
+SCENES_HEADER = os.path.join(HERE, "..", "include", "anystereo_scenes.h")
+
+
+def build_scenes(force: bool = False, verbose: bool = True) -> str:
+    """The same recipe as the main library: the same flags, objects under build/scenes/, the source hash compiled in
+    (`scn_source_hash`; `_scenes_lib.load()` refuses a stale binary)."""
+    os.makedirs(SCENES_OBJ, exist_ok=True)
+    os.makedirs(LIBDIR, exist_ok=True)
+    srcs = sorted(f for f in os.listdir(SCENES_CSRC) if f.endswith(".hip"))
+    stamp_src = os.path.join(SCENES_OBJ, "stamp.cpp")
+    stamp = 'extern "C" const char* scn_source_hash(void) { return "%s"; }\n' % _srchash().scenes_source_hash()
+    if not os.path.exists(stamp_src) or open(stamp_src).read() != stamp:
+        open(stamp_src, "w").write(stamp)
+    deps = [os.path.join(SCENES_CSRC, f) for f in sorted(os.listdir(SCENES_CSRC)) if f.endswith(".h")] + [SCENES_HEADER]
+    hipcc = _hipcc()
+    objs, compiled = [], False
+    for s in srcs:
+        src, obj = os.path.join(SCENES_CSRC, s), os.path.join(SCENES_OBJ, s[:-4] + ".o")
+        objs.append(obj)
+        if force or _newer([src] + deps, obj):
+            r = subprocess.run([hipcc] + FLAGS + ["-c", src, "-o", obj], capture_output=True, text=True)
+            if verbose and (r.stderr.strip() or r.returncode):
+                sys.stderr.write(r.stderr)
+            if r.returncode != 0:
+                raise RuntimeError(f"hipcc failed on {src}")
+            compiled = True
+            if verbose:
+                print(f"[build] compiled scenes/{s}")
+    if force or compiled or _newer(objs + [stamp_src], SCENES_LIB):
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SCENES_LIB] + objs + [stamp_src], capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr)
+            raise RuntimeError("link failed")
+        if verbose:
+            print(f"[build] linked {SCENES_LIB}")
+    return SCENES_LIB
 
 
 def build(force: bool = False, verbose: bool = True) -> str:
@@ -86,6 +133,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             raise RuntimeError("link failed")
         if verbose:
             print(f"[build] linked {LIB}")
+    build_scenes(force=force, verbose=verbose)
     return LIB
 
 

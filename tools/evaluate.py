@@ -14,6 +14,9 @@ has disparity k everywhere, so the right view's ground truth is k as well.  One 
                                                                     # one field query per entry); the metrics become lists in that order
     python tools/evaluate.py --pairs 4 --baseline bicubic           # plus the reference's interpolation baseline (multi_evaothers): this
                                                                     # model's own scale-1 output, un-padded, times scale, bicubic resize
+    python tools/evaluate.py --pairs 8 --scenes --scene-layers 6    # procedural scenes (harness/scenes.py) instead of the rolled image: a
+                                                                    # non-constant ground truth, a right-view ground truth that differs from
+                                                                    # it and a non-empty occluded region, all made on the device
 
 The weights are the deterministic fill, so EPE here says nothing about a trained model: the
 line shows that the protocol runs on the device, what it counts and how fast.  No dataset readers.
@@ -70,7 +73,18 @@ def parse_args(argv=None):
                     help="evaluate these GRU iterations (1-based, ascending, each at most --iters) from one encoded pass per pair")
     ap.add_argument("--baseline", default=None, choices=["bicubic"],
                     help="also evaluate the interpolation baseline: the scale-1 query of the same pass resized bicubically")
+    ap.add_argument("--scenes", action="store_true",
+                    help="evaluate on procedural scenes (harness/scenes.py: pair, ground truth, right-view ground truth / exact occlusion "
+                         "mask made on the device) instead of the rolled synthetic pair; --shift is then unused")
+    ap.add_argument("--scene-layers", type=int, default=None, metavar="K",
+                    help="with --scenes: the layers of a scene, the background included (1..8); default: SceneSpec's 6")
     a = ap.parse_args(argv)
+    if a.scene_layers is not None and not a.scenes:
+        ap.error("--scene-layers needs --scenes")
+    if a.scene_layers is not None and not 1 <= a.scene_layers <= 8:
+        ap.error(f"--scene-layers {a.scene_layers}: 1..8 expected")
+    if a.scenes and a.uint8:
+        ap.error("--scenes renders float images: --uint8 is for the rolled pair")
     if a.curve is not None:
         try:
             a.curve = tuple(int(k) for k in a.curve.split(","))
@@ -79,6 +93,14 @@ def parse_args(argv=None):
         if any(k < 1 or k > a.iters for k in a.curve) or list(a.curve) != sorted(set(a.curve)):
             ap.error(f"--curve {a.curve}: ascending distinct GRU iterations in [1, --iters = {a.iters}] expected")
     return a
+
+
+def _scene_info(a):
+    """What --scenes adds to the result line (without it the line is as it always was)."""
+    from anystereo import _scenes_lib
+    from anystereo.harness.scenes import SceneSpec
+    return {"data": "scenes", "scene_layers": a.scene_layers or SceneSpec().n_layers, "gt_disparity": None,
+            "scenes_library": _scenes_lib.library_info()}
 
 
 def main():
@@ -106,7 +128,16 @@ def main():
     fill_module_deterministic(model, base_seed=1)
     model = model.to(dev)
 
+    def scene_pairs():
+        from anystereo.harness.scenes import SceneSpec, scene_pairs as one_scene
+        spec = SceneSpec(aspect=a.height / a.width, **({} if a.scene_layers is None else {"n_layers": a.scene_layers})).validate()
+        for i in dist.shard_indices(a.pairs, rank, world):
+            yield from one_scene(spec, 1000, 1, a.height, a.width, protocol=a.protocol, device=dev, index0=i)
+
     def pairs():
+        if a.scenes:
+            yield from scene_pairs()
+            return
         for i in dist.shard_indices(a.pairs, rank, world):
             i1, i2 = synthetic_pair(1, a.height, a.width, shift=a.shift, seed=1000 + i)
             if a.uint8:
@@ -146,7 +177,7 @@ def main():
                           "image_dtype": "uint8" if a.uint8 else "float32", "iters": a.iters, "gt_disparity": a.shift,
                           "weights": "deterministic fill", "model_max_disp": args.max_disp, "lsp_window": [args.lsp_height, args.lsp_width], "pairs_per_s": round(sum(rates), 3),
                           "per_rank_pairs_per_s": [round(r, 3) for r in rates], "rank0_pairs": local_pairs,
-                          "library": _lib.library_info(), **({"images_written": int(sum(written))} if sink is not None else {}),
+                          "library": _lib.library_info(), **(_scene_info(a) if a.scenes else {}), **({"images_written": int(sum(written))} if sink is not None else {}),
                           **merged}))
 
 
