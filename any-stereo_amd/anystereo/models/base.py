@@ -110,7 +110,7 @@ class ContinuousStereoBase(nn.Module):
         if G.needs_grad(disp, x, *self.liif_up.parameters()):
             return self._hot_upsample_train(disp, feats, hr_coord, scale_vec)
         logits = self.liif_up(feats, hr_coord, scale_vec)  # [B,9,Q]
-        hr_coord.clamp_(-1 + 1e-6, 1 - 1e-6)  # side effect of context_upsample_multiscale_train (submodule.py:366)
+        AF.clamp_hr_coord(hr_coord)  # side effect of context_upsample_multiscale_train (submodule.py:366)
         with scope("convex_upsample"):
             return ops.convex_upsample(disp, logits, hr_coord, scale=scale_vec, mask_is_logits=True)
 
@@ -136,7 +136,7 @@ class ContinuousStereoBase(nn.Module):
                 up = (G.ConvexUpsampleQuater.apply(d, logits, hr, sv, True) if train
                       else ops.convex_upsample_quater(d, logits, hr, scale=sv, mask_is_logits=True))
             else:
-                hr.clamp_(-1 + 1e-6, 1 - 1e-6)  # side effect of context_upsample_multiscale_train (submodule.py:366)
+                AF.clamp_hr_coord(hr)  # side effect of context_upsample_multiscale_train (submodule.py:366)
                 up = (G.ConvexUpsample.apply(d, logits, hr, sv, True) if train
                       else ops.convex_upsample(d, logits, hr, scale=sv, mask_is_logits=True))
         if norm:
@@ -169,9 +169,9 @@ class ContinuousStereoBase(nn.Module):
         order = self._query_order(hr_coord, sizes) if (self.sort_queries and len(feats) <= 2) else None
         hr = hr_coord if order is None else torch.gather(hr_coord, 1, order[0].unsqueeze(-1).expand(-1, -1, 2))
         logits = self.liif_up(feats, hr, scale_vec)
-        hr_coord.clamp_(-1 + 1e-6, 1 - 1e-6)  # reference side effect (submodule.py:366)
+        AF.clamp_hr_coord(hr_coord)  # reference side effect (submodule.py:366)
         if order is not None:
-            hr = hr.clamp(-1 + 1e-6, 1 - 1e-6)
+            hr = AF.clamp_hr_coord(hr, inplace=False)
         with scope("convex_upsample"):
             out = G.ConvexUpsample.apply(disp, logits.contiguous(), hr, scale_vec, True)
         return out if order is None else torch.gather(out, 2, order[1].unsqueeze(1))
@@ -481,7 +481,7 @@ class ContinuousStereoBase(nn.Module):
             up = self.upsample_disp(torch.cat([d for d, _ in part], 0), torch.cat([h for _, h in part], 0), rep(stem_4x), s2,
                                     rep(stem_1x), hr_coord=hc, scale=rep(sc).contiguous())
             preds.extend(up.split(b, 0))
-        hr_coord.clamp_(-1 + 1e-6, 1 - 1e-6)  # the reference's side effect on the caller's tensor (submodule.py:366)
+        AF.clamp_hr_coord(hr_coord)  # the reference's side effect on the caller's tensor (submodule.py:366)
         return list(preds)
 
     def _iterate(self, lookup_fn, net_list, inp_list, disp, coords, iters, test_mode, stem_4x, stem_2x, hr_coord, scale, stem_1x=None):

@@ -37,11 +37,19 @@ def softmax_disparity_regression(cost):
         return ops.disparity_regression(cost, apply_softmax=True)
 
 
+def clamp_hr_coord(hr_coord, inplace=True):
+    """The reference's clamp of the query coordinates to [-1 + 1e-6, 1 - 1e-6] (submodule.py:366): Python doubles, which torch
+    rounds to the tensor's dtype (fp32: kCoordLo / kCoordHi of csrc/query.h).  In place (the default) it is the reference's side
+    effect on the caller's tensor; `inplace=False` returns a clamped copy."""
+    lo, hi = -1 + 1e-6, 1 - 1e-6
+    return hr_coord.clamp_(lo, hi) if inplace else hr_coord.clamp(lo, hi)
+
+
 def context_upsample_multiscale_train(disp_low, up_weights, hr_coord):
     """Convex 3x3 upsampling at arbitrary query coordinates -> [B,Q].
     disp_low [B,1,h,w] (already scaled), up_weights [B,9,Q] (already softmaxed), hr_coord [B,Q,2].
     Like the reference (submodule.py:366) this clamps `hr_coord` IN PLACE."""
-    hr_coord.clamp_(-1 + 1e-6, 1 - 1e-6)
+    clamp_hr_coord(hr_coord)
     d, m, c = disp_low.float().contiguous(), up_weights.float().contiguous(), hr_coord.float().contiguous()
     if G.needs_grad(d, m):
         return G.ConvexUpsample.apply(d, m, c, None, False)[:, 0]

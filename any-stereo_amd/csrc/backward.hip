@@ -6,6 +6,7 @@
 // scatter kernels, which clear their destination on the same stream and accumulate with float atomics exactly like
 // the reference's grid_sample backward does.
 #include "common.h"
+#include "query.h"
 
 namespace {
 
@@ -118,10 +119,7 @@ __global__ __launch_bounds__(256) void dispreg_bwd_kernel(const float* __restric
 }
 
 // ---- a14ᵀ: nearest gather (liif.py:108-137) ---------------------------------------------------------------------
-__device__ __forceinline__ int nearest_idx_b(float c, int n) {
-  const float u = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(c, 1.f), (float)n), 1.f), 2.f);
-  return (int)rintf(u);
-}
+using as::cell_centre, as::cell_rel_to, as::clamp_coord, as::nearest_idx;
 
 // Scatter-add of per-query rows into the low-resolution map.  Lanes whose queries fall into the same source pixel are
 // first summed inside the wave (segmented suffix sum over runs of equal keys, 6 shuffle steps) and only the head of
@@ -135,8 +133,8 @@ __global__ __launch_bounds__(256) void liif_gather_bwd_kernel(const float* __res
   const bool valid = t < (long long)B * Q;  // no early return: every lane takes part in the shuffles
   const long long tt = valid ? t : 0;
   const long long b = tt / Q, q = tt - b * Q;
-  const int iy = nearest_idx_b(fminf(fmaxf(coord[tt * 2 + 0], lo), hi), H);
-  const int ix = nearest_idx_b(fminf(fmaxf(coord[tt * 2 + 1], lo), hi), W);
+  const int iy = nearest_idx(clamp_coord(coord[tt * 2 + 0], lo, hi), H);
+  const int ix = nearest_idx(clamp_coord(coord[tt * 2 + 1], lo, hi), W);
   const bool ok = valid && iy >= 0 && iy < H && ix >= 0 && ix < W;
   const long long plane = (long long)H * W;
   const int key = ok ? (int)(b * plane + (long long)iy * W + ix) : -1;
@@ -225,13 +223,12 @@ __global__ __launch_bounds__(256) void liif_rel_key_kernel(RelParams p) {
   const float cr = p.coord[t * 2 + 0], cc = p.coord[t * 2 + 1];
   int key = 0;
   for (int s = 0; s < p.n_src; ++s) {
-    const int iy = nearest_idx_b(fminf(fmaxf(cr, p.lo), p.hi), p.H[s]);
-    const int ix = nearest_idx_b(fminf(fmaxf(cc, p.lo), p.hi), p.W[s]);
+    const int iy = nearest_idx(clamp_coord(cr, p.lo, p.hi), p.H[s]);
+    const int ix = nearest_idx(clamp_coord(cc, p.lo, p.hi), p.W[s]);
     if (p.rel) {
-      const float qy = __fadd_rn(p.c0y[s], __fmul_rn(p.sy[s], (float)iy));
-      const float qx = __fadd_rn(p.c0x[s], __fmul_rn(p.sx[s], (float)ix));
-      p.rel[(b * 2 * p.n_src + 2 * s) * p.Q + q] = __fmul_rn(__fsub_rn(cr, qy), (float)p.H[s]);
-      p.rel[(b * 2 * p.n_src + 2 * s + 1) * p.Q + q] = __fmul_rn(__fsub_rn(cc, qx), (float)p.W[s]);
+      const float qy = cell_centre(p.c0y[s], p.sy[s], iy), qx = cell_centre(p.c0x[s], p.sx[s], ix);
+      p.rel[(b * 2 * p.n_src + 2 * s) * p.Q + q] = cell_rel_to(cr, qy, p.H[s]);
+      p.rel[(b * 2 * p.n_src + 2 * s + 1) * p.Q + q] = cell_rel_to(cc, qx, p.W[s]);
     }
     key = s == 0 ? (iy * p.W[0] + ix) * 4 : key + ((iy & 1) << 1) + (ix & 1);
   }
@@ -270,8 +267,8 @@ __global__ __launch_bounds__(256) void convex_bwd_kernel(const float* __restrict
 #pragma unroll
     for (int k = 0; k < 9; ++k) l[k] /= s;
   }
-  const int iy = nearest_idx_b(fminf(fmaxf(coord[t * 2 + 0], lo), hi), H);
-  const int ix = nearest_idx_b(fminf(fmaxf(coord[t * 2 + 1], lo), hi), W);
+  const int iy = nearest_idx(clamp_coord(coord[t * 2 + 0], lo, hi), H);
+  const int ix = nearest_idx(clamp_coord(coord[t * 2 + 1], lo, hi), W);
   const float* dp = disp + b * H * W;
   const float mul = scale ? __fmul_rn(4.f, scale[b]) : 1.f;
   const float g = valid ? dout[t] : 0.f;
@@ -720,7 +717,7 @@ int as_liif_gather_bwd(const float* d_latent, const float* coord, float* d_feat,
   const int zrc = as::zero_fill(d_feat, (long long)B * C * H * W, as::as_stream(stream));
   if (zrc != AS_OK) return zrc;
   hipLaunchKernelGGL(liif_gather_bwd_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream),
-                     d_latent, coord, d_feat, B, C, H, W, Q, lat_ctot, lat_coff, (float)(-1.0 + 1e-6), (float)(1.0 - 1e-6));
+                     d_latent, coord, d_feat, B, C, H, W, Q, lat_ctot, lat_coff, as::kCoordLo, as::kCoordHi);
   return as::check_launch("liif_gather_bwd");
 }
 
@@ -743,11 +740,7 @@ int as_liif_rel_key(const float* coord, float* rel, int* key, int B, int Q, int 
   RelParams p{};
   p.coord = coord; p.rel = rel; p.key = key; p.B = B; p.Q = Q; p.n_src = n_src;
   p.H[0] = H0; p.W[0] = W0; p.H[1] = n_src > 1 ? H1 : 1; p.W[1] = n_src > 1 ? W1 : 1;
-  p.lo = (float)(-1.0 + 1e-6); p.hi = (float)(1.0 - 1e-6);
-  for (int s = 0; s < 2; ++s) {
-    p.c0y[s] = (float)(-1.0 + 1.0 / p.H[s]); p.sy[s] = (float)(2.0 * (1.0 / p.H[s]));
-    p.c0x[s] = (float)(-1.0 + 1.0 / p.W[s]); p.sx[s] = (float)(2.0 * (1.0 / p.W[s]));
-  }
+  as::set_query_cells(p);
   hipLaunchKernelGGL(liif_rel_key_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream), p);
   return as::check_launch("liif_rel_key");
 }
@@ -762,8 +755,8 @@ int as_convex_upsample_bwd(const float* disp, const float* scale, const float* m
     if (zrc != AS_OK) return zrc;
   }
   hipLaunchKernelGGL(convex_bwd_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream),
-                     disp, scale, mask, coord, d_out, d_mask, d_disp, B, H, W, Q, mask_is_logits, (float)(-1.0 + 1e-6),
-                     (float)(1.0 - 1e-6));
+                     disp, scale, mask, coord, d_out, d_mask, d_disp, B, H, W, Q, mask_is_logits, as::kCoordLo,
+                     as::kCoordHi);
   return as::check_launch("convex_upsample_bwd");
 }
 

@@ -3,8 +3,11 @@
 // All HBM/L2-bound gathers and stencils; lanes = consecutive pixels / consecutive queries so every
 // store is a coalesced wave store.
 #include "common.h"
+#include "query.h"
 
 namespace {
+
+using as::cell_centre, as::cell_rel, as::cell_rel_to, as::clamp_coord, as::nearest_idx;
 
 // ---- structure feature: out = cat(x, affinity(x)) -------------------------------------------------
 // pass 1: copy x into out[:, :C] and write the clamped L2 norm over channels to ws[b,y,x]
@@ -84,20 +87,13 @@ __global__ __launch_bounds__(256) void sf_affinity_kernel(const float* __restric
   for (int j = 0; j < 8; ++j) op[(long long)j * plane] = ok[j] ? fmaxf(acc[j] / (n0 * nn[j]), 0.f) : 0.f;
 }
 
-// grid_sample(mode='nearest', align_corners=False) source index, evaluated with the same fp32
-// operation sequence as ATen (no fma contraction): nearbyint(((c + 1) * n - 1) / 2)
-__device__ __forceinline__ int nearest_idx(float c, int n) {
-  const float u = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(c, 1.f), (float)n), 1.f), 2.f);
-  return (int)rintf(u);
-}
-
 struct GatherParams {
   const float* feat;
   const float* coord;
   float* latent;
   int B, C, H, W, Q, lat_ctot, lat_coff;
-  float lo, hi;               // clamp bounds (float)(-1+1e-6), (float)(1-1e-6)
-  float c0y, sy, c0x, sx;     // make_coord: centre(i) = c0 + s*i, c0 = (float)(-1+1/n), s = (float)(2/n)
+  float lo, hi;               // clamp bounds (query.h: kCoordLo, kCoordHi)
+  float c0y, sy, c0x, sx;     // make_coord of the source map (query.h: coord_axis): centre(i) = c0 + s*i
 };
 
 __global__ __launch_bounds__(256) void liif_gather_kernel(GatherParams p) {
@@ -106,18 +102,18 @@ __global__ __launch_bounds__(256) void liif_gather_kernel(GatherParams p) {
   const int b = (int)(t / p.Q);
   const int q = (int)(t - (long long)b * p.Q);
   const float cr = p.coord[t * 2 + 0], cc = p.coord[t * 2 + 1];
-  const int iy = nearest_idx(fminf(fmaxf(cr, p.lo), p.hi), p.H);
-  const int ix = nearest_idx(fminf(fmaxf(cc, p.lo), p.hi), p.W);
+  const int iy = nearest_idx(clamp_coord(cr, p.lo, p.hi), p.H);
+  const int ix = nearest_idx(clamp_coord(cc, p.lo, p.hi), p.W);
   const bool ok = iy >= 0 && iy < p.H && ix >= 0 && ix < p.W;  // always true after the clamp
   const long long plane = (long long)p.H * p.W;
   const float* fp = p.feat + (long long)b * p.C * plane + (ok ? (long long)iy * p.W + ix : 0);
   float* lp = p.latent + ((long long)b * p.lat_ctot + p.lat_coff) * p.Q + q;
   for (int c = 0; c < p.C; ++c) lp[(long long)c * p.Q] = ok ? fp[(long long)c * plane] : 0.f;
-  // rel = (coord_unclamped - cell_centre) * (H, W)   (liif.py:127-129)
-  const float qy = ok ? __fadd_rn(p.c0y, __fmul_rn(p.sy, (float)iy)) : 0.f;
-  const float qx = ok ? __fadd_rn(p.c0x, __fmul_rn(p.sx, (float)ix)) : 0.f;
-  lp[(long long)p.C * p.Q] = __fmul_rn(__fsub_rn(cr, qy), (float)p.H);
-  lp[(long long)(p.C + 1) * p.Q] = __fmul_rn(__fsub_rn(cc, qx), (float)p.W);
+  // rel = (coord_unclamped - cell_centre) * (H, W)   (liif.py:127-129); the centre of a cell outside the map is 0
+  const float qy = ok ? cell_centre(p.c0y, p.sy, iy) : 0.f;
+  const float qx = ok ? cell_centre(p.c0x, p.sx, ix) : 0.f;
+  lp[(long long)p.C * p.Q] = cell_rel_to(cr, qy, p.H);
+  lp[(long long)(p.C + 1) * p.Q] = cell_rel_to(cc, qx, p.W);
 }
 
 // ---- a14 + first layer of a15 fused -----------------------------------------------------------
@@ -145,7 +141,7 @@ __global__ __launch_bounds__(256) void liif_mlp1_gather_kernel(Mlp1Params p) {
   const int b = (int)(t / p.Q);
   const int q = (int)(t - (long long)b * p.Q);
   const float cr = p.coord[t * 2 + 0], cc = p.coord[t * 2 + 1];
-  const float crc = fminf(fmaxf(cr, p.lo), p.hi), ccc = fminf(fmaxf(cc, p.lo), p.hi);
+  const float crc = clamp_coord(cr, p.lo, p.hi), ccc = clamp_coord(cc, p.lo, p.hi);
   const float* up[2];
   long long plane[2];
   float rel[4];
@@ -155,10 +151,8 @@ __global__ __launch_bounds__(256) void liif_mlp1_gather_kernel(Mlp1Params p) {
       const int iy = nearest_idx(crc, p.H[s]), ix = nearest_idx(ccc, p.W[s]);
       plane[s] = (long long)p.H[s] * p.W[s];
       up[s] = p.u[s] + (long long)b * p.C * plane[s] + (long long)iy * p.W[s] + ix;
-      const float qy = __fadd_rn(p.c0y[s], __fmul_rn(p.sy[s], (float)iy));
-      const float qx = __fadd_rn(p.c0x[s], __fmul_rn(p.sx[s], (float)ix));
-      rel[2 * s] = __fmul_rn(__fsub_rn(cr, qy), (float)p.H[s]);
-      rel[2 * s + 1] = __fmul_rn(__fsub_rn(cc, qx), (float)p.W[s]);
+      rel[2 * s] = cell_rel(cr, p.c0y[s], p.sy[s], iy, p.H[s]);
+      rel[2 * s + 1] = cell_rel(cc, p.c0x[s], p.sx[s], ix, p.W[s]);
     } else {
       up[s] = p.u[0];
       plane[s] = 0;
@@ -216,8 +210,8 @@ __global__ __launch_bounds__(256) void softmax_convex_kernel(const float* __rest
       s += l[k];
     }
   }
-  const int iy = nearest_idx(fminf(fmaxf(coord[t * 2 + 0], lo), hi), H);
-  const int ix = nearest_idx(fminf(fmaxf(coord[t * 2 + 1], lo), hi), W);
+  const int iy = nearest_idx(clamp_coord(coord[t * 2 + 0], lo, hi), H);
+  const int ix = nearest_idx(clamp_coord(coord[t * 2 + 1], lo, hi), W);
   const float* dp = disp + (long long)b * H * W;
   const float sc = scale ? scale[b] : 1.f;
   const float four = scale ? 4.f : 1.f;
@@ -254,9 +248,9 @@ int as_liif_gather(const float* feat, const float* coord, float* latent, int B, 
   GatherParams p{};
   p.feat = feat; p.coord = coord; p.latent = latent;
   p.B = B; p.C = C; p.H = H; p.W = W; p.Q = Q; p.lat_ctot = lat_ctot; p.lat_coff = lat_coff;
-  p.lo = (float)(-1.0 + 1e-6); p.hi = (float)(1.0 - 1e-6);
-  p.c0y = (float)(-1.0 + 1.0 / H); p.sy = (float)(2.0 * (1.0 / H));
-  p.c0x = (float)(-1.0 + 1.0 / W); p.sx = (float)(2.0 * (1.0 / W));
+  p.lo = as::kCoordLo; p.hi = as::kCoordHi;
+  const as::CoordAxis ay = as::coord_axis(H), ax = as::coord_axis(W);
+  p.c0y = ay.c0; p.sy = ay.s; p.c0x = ax.c0; p.sx = ax.s;
   hipLaunchKernelGGL(liif_gather_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream), p);
   return as::check_launch("liif_gather");
 }
@@ -270,11 +264,7 @@ int as_liif_gather_mlp1(const float* u0, const float* u1, const float* coord, co
   p.u[0] = u0; p.u[1] = u1; p.coord = coord; p.wrel = wrel; p.bias = bias; p.out = out;
   p.B = B; p.C = C; p.Q = Q; p.n_src = u1 ? 2 : 1;
   p.H[0] = H0; p.W[0] = W0; p.H[1] = u1 ? H1 : 1; p.W[1] = u1 ? W1 : 1;
-  p.lo = (float)(-1.0 + 1e-6); p.hi = (float)(1.0 - 1e-6);
-  for (int s = 0; s < 2; ++s) {
-    p.c0y[s] = (float)(-1.0 + 1.0 / p.H[s]); p.sy[s] = (float)(2.0 * (1.0 / p.H[s]));
-    p.c0x[s] = (float)(-1.0 + 1.0 / p.W[s]); p.sx[s] = (float)(2.0 * (1.0 / p.W[s]));
-  }
+  as::set_query_cells(p);
   hipLaunchKernelGGL(liif_mlp1_gather_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream), p);
   return as::check_launch("liif_gather_mlp1");
 }
@@ -284,7 +274,7 @@ int as_convex_upsample(const float* disp, const float* scale, const float* mask,
   AS_REQUIRE(disp && mask && coord && out, AS_ERR_BAD_ARG, "convex_upsample: null pointer");
   AS_REQUIRE(B > 0 && H > 0 && W > 0 && Q > 0, AS_ERR_BAD_ARG, "convex_upsample: non-positive size");
   hipLaunchKernelGGL(softmax_convex_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream),
-                     disp, scale, mask, coord, out, B, H, W, Q, mask_is_logits, (float)(-1.0 + 1e-6), (float)(1.0 - 1e-6));
+                     disp, scale, mask, coord, out, B, H, W, Q, mask_is_logits, as::kCoordLo, as::kCoordHi);
   return as::check_launch("convex_upsample");
 }
 

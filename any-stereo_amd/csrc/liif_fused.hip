@@ -22,11 +22,12 @@
 #include <algorithm>
 
 #include "common.h"
+#include "query.h"
 #include "split.h"
 
 namespace {
 
-using namespace as;  // split.h: vector types, join_fma / join, split_mfma_*, the pack kernels' split_part_clamp
+using namespace as;  // split.h: vector types, join_fma / join, split_mfma_*, the pack kernels' split_part_clamp; query.h: the query's cell
 
 constexpr int kHid1 = 128, kHid2 = 64, kHid3 = 64, kOut = 9;
 constexpr int kFragBlocks = 64;                      // 1-KiB fragment blocks of the weight image (see liif_tail_pack_kernel)
@@ -76,12 +77,6 @@ __device__ __forceinline__ void split8_pos(const float (&v)[8], half8& hi, half8
 __device__ __forceinline__ float relu_bits(float x) { return __builtin_bit_cast(float, max(__builtin_bit_cast(int, x), 0)); }
 
 __device__ unsigned g_split_overflow_liif;  // queries / pixels whose operands left the fp16 range (as_split_overflow_count)
-
-// grid_sample(mode='nearest', align_corners=False) source index with ATen's fp32 operation sequence (no fma contraction)
-__device__ __forceinline__ int nearest_idx(float c, int n) {
-  const float u = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(c, 1.f), (float)n), 1.f), 2.f);
-  return (int)rintf(u);
-}
 
 __device__ __forceinline__ int acc_row(int i, int half) { return (i & 3) + 8 * (i >> 2) + 4 * half; }
 
@@ -511,7 +506,7 @@ __device__ __forceinline__ void tile_prepare(const TailParams& p, const float* _
   x.t = t;
   x.valid = valid;
   const int b = (int)(t / p.Q);
-  const float crc = fminf(fmaxf(cr, p.lo), p.hi), ccc = fminf(fmaxf(cc, p.lo), p.hi);
+  const float crc = clamp_coord(cr, p.lo, p.hi), ccc = clamp_coord(cc, p.lo, p.hi);
   if (p.clamp_inplace && valid && half == 0) {   // the reference clamps the caller's tensor in place (submodule.py:366)
     p.coord[t * 2 + 0] = crc;
     p.coord[t * 2 + 1] = ccc;
@@ -527,10 +522,8 @@ __device__ __forceinline__ void tile_prepare(const TailParams& p, const float* _
     if (s == 0) x.up0 = up; else x.up1 = up;
     x.pix[s] = iy * p.W[s] + ix;
     if (s == 1) x.bsrc1 = bs;
-    const float qy = __fadd_rn(p.c0y[s], __fmul_rn(p.sy[s], (float)iy));
-    const float qx = __fadd_rn(p.c0x[s], __fmul_rn(p.sx[s], (float)ix));
-    rel[2 * s] = __fmul_rn(__fsub_rn(cr, qy), (float)p.H[s]);          // (coord_unclamped - cell centre) * (H, W)
-    rel[2 * s + 1] = __fmul_rn(__fsub_rn(cc, qx), (float)p.W[s]);
+    rel[2 * s] = cell_rel(cr, p.c0y[s], p.sy[s], iy, p.H[s]);
+    rel[2 * s + 1] = cell_rel(cc, p.c0x[s], p.sx[s], ix, p.W[s]);
   }
   if (NSRC == 1) { x.up1 = x.up0; x.pix[1] = 0; x.bsrc1 = b; }
 #pragma unroll
@@ -1401,11 +1394,7 @@ static int liif_tail_impl(const float* u0, const float* u1, float* coord, const 
   p.out = out; p.logits = logits; p.B = B; p.Q = Q; p.n_src = u1 ? 2 : 1; p.clamp_inplace = clamp_inplace;
   p.H[0] = H0; p.W[0] = W0; p.H[1] = u1 ? H1 : 1; p.W[1] = u1 ? W1 : 1; p.Hd = Hd; p.Wd = Wd;
   p.total = (long long)B * Q;
-  p.lo = (float)(-1.0 + 1e-6); p.hi = (float)(1.0 - 1e-6);
-  for (int s = 0; s < 2; ++s) {
-    p.c0y[s] = (float)(-1.0 + 1.0 / p.H[s]); p.sy[s] = (float)(2.0 * (1.0 / p.H[s]));
-    p.c0x[s] = (float)(-1.0 + 1.0 / p.W[s]); p.sx[s] = (float)(2.0 * (1.0 / p.W[s]));
-  }
+  as::set_query_cells(p);
   const long long tiles = as::cdiv64(p.total, 32);
   AS_REQUIRE(tiles < 2147483647ll, AS_ERR_BAD_SHAPE, "liif_tail: too many queries");
   p.tiles = (int)tiles;
@@ -1455,11 +1444,7 @@ static int mlp_params(TailParams& p, const float* u0, const float* u1, const flo
   p.B = B; p.Q = Q; p.n_src = u1 ? 2 : 1; p.clamp_inplace = 0; p.B1 = B1;
   p.H[0] = H0; p.W[0] = W0; p.H[1] = u1 ? H1 : 1; p.W[1] = u1 ? W1 : 1; p.Hd = 1; p.Wd = 1;
   p.total = (long long)B * Q;
-  p.lo = (float)(-1.0 + 1e-6); p.hi = (float)(1.0 - 1e-6);
-  for (int s = 0; s < 2; ++s) {
-    p.c0y[s] = (float)(-1.0 + 1.0 / p.H[s]); p.sy[s] = (float)(2.0 * (1.0 / p.H[s]));
-    p.c0x[s] = (float)(-1.0 + 1.0 / p.W[s]); p.sx[s] = (float)(2.0 * (1.0 / p.W[s]));
-  }
+  as::set_query_cells(p);
   const long long tiles = as::cdiv64(p.total, 32);
   AS_REQUIRE(tiles < 2147483647ll, AS_ERR_BAD_SHAPE, "%s: too many queries", what);
   p.tiles = (int)tiles;

@@ -4,13 +4,11 @@
 // the [B, ctot, Q] latent that the 1x1-conv MLP reads.  HBM/L2-bound gathers; lanes = consecutive queries, so every
 // store is one coalesced wave store.
 #include "common.h"
+#include "query.h"
 
 namespace {
 
-__device__ __forceinline__ int nearest_idx(float c, int n) {  // grid_sample(nearest, align_corners=False), ATen's op order
-  const float u = __fdiv_rn(__fsub_rn(__fmul_rn(__fadd_rn(c, 1.f), (float)n), 1.f), 2.f);
-  return (int)rintf(u);
-}
+using as::cell_centre, as::cell_rel_to, as::clamp_coord, as::nearest_idx;
 
 struct LatentParams {
   const float* feat;    // [B,C,H,W]
@@ -25,7 +23,7 @@ struct LatentParams {
   int n_enc;
   float sh_y[2], sh_x[2];   // (float)(v * r + 1e-6) for v = -1, +1
   float lo, hi;
-  float c0y, sy, c0x, sx;   // make_coord: centre(i) = c0 + s*i
+  float c0y, sy, c0x, sx;   // make_coord (query.h: coord_axis): centre(i) = c0 + s*i
 };
 
 __device__ __forceinline__ void sample_index(const LatentParams& p, float cr, float cc, int s, int& iy, int& ix) {
@@ -34,8 +32,8 @@ __device__ __forceinline__ void sample_index(const LatentParams& p, float cr, fl
     r = __fadd_rn(cr, p.sh_y[s >> 1]);
     c = __fadd_rn(cc, p.sh_x[s & 1]);
   }
-  iy = nearest_idx(fminf(fmaxf(r, p.lo), p.hi), p.H);
-  ix = nearest_idx(fminf(fmaxf(c, p.lo), p.hi), p.W);
+  iy = nearest_idx(clamp_coord(r, p.lo, p.hi), p.H);
+  ix = nearest_idx(clamp_coord(c, p.lo, p.hi), p.W);
   iy = min(max(iy, 0), p.H - 1);  // no-ops after the clamp (kept so that a NaN coordinate cannot index outside the map)
   ix = min(max(ix, 0), p.W - 1);
 }
@@ -53,8 +51,8 @@ __global__ __launch_bounds__(256) void latent_kernel(LatentParams p) {
   for (int s = 0; s < p.n_samp; ++s) {
     int iy, ix;
     sample_index(p, cr, cc, s, iy, ix);
-    cy[s] = __fadd_rn(p.c0y, __fmul_rn(p.sy, (float)iy));
-    cx[s] = __fadd_rn(p.c0x, __fmul_rn(p.sx, (float)ix));
+    cy[s] = cell_centre(p.c0y, p.sy, iy);
+    cx[s] = cell_centre(p.c0x, p.sx, ix);
     if (!p.unfold9) {
       const float* fp = fb + (long long)iy * p.W + ix;
       int c = 0;
@@ -88,8 +86,8 @@ __global__ __launch_bounds__(256) void latent_kernel(LatentParams p) {
     qy = __fdiv_rn(__fadd_rn(cy[0], cy[3]), 2.f);
     qx = __fdiv_rn(__fadd_rn(cx[0], cx[3]), 2.f);
   }
-  const float ry = __fmul_rn(__fsub_rn(cr, qy), (float)p.H);
-  const float rx = __fmul_rn(__fsub_rn(cc, qx), (float)p.W);
+  const float ry = cell_rel_to(cr, qy, p.H);
+  const float rx = cell_rel_to(cc, qx, p.W);
   lp[0] = ry;
   lp[p.Q] = rx;
   lp += 2ll * p.Q;
@@ -192,7 +190,7 @@ __global__ __launch_bounds__(256) void convex_quater_kernel(const float* __restr
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float r = __fadd_rn(cr, (k >> 1) ? shy1 : shy0), c = __fadd_rn(cc, (k & 1) ? shx1 : shx0);
-    int iy = nearest_idx(fminf(fmaxf(r, lo), hi), H), ix = nearest_idx(fminf(fmaxf(c, lo), hi), W);
+    int iy = nearest_idx(clamp_coord(r, lo, hi), H), ix = nearest_idx(clamp_coord(c, lo, hi), W);
     iy = min(max(iy, 0), H - 1);
     ix = min(max(ix, 0), W - 1);
     const float d = __fmul_rn(__fmul_rn(dp[(long long)iy * W + ix], four), sc);
@@ -312,7 +310,7 @@ __global__ __launch_bounds__(256) void convex_quater_bwd_kernel(const float* __r
 #pragma unroll
   for (int k = 0; k < 4; ++k) {
     const float r = __fadd_rn(cr, (k >> 1) ? shy1 : shy0), c = __fadd_rn(cc, (k & 1) ? shx1 : shx0);
-    int iy = nearest_idx(fminf(fmaxf(r, lo), hi), H), ix = nearest_idx(fminf(fmaxf(c, lo), hi), W);
+    int iy = nearest_idx(clamp_coord(r, lo, hi), H), ix = nearest_idx(clamp_coord(c, lo, hi), W);
     iy = min(max(iy, 0), H - 1);
     ix = min(max(ix, 0), W - 1);
     d[k] = dp[(long long)iy * W + ix] * mul;
@@ -337,9 +335,9 @@ int fill(LatentParams& p, const float* feat, const float* coord, const float* em
   p.feat = feat; p.coord = coord; p.emb = emb; p.cell = cell; p.latent = latent;
   p.B = B; p.C = C; p.H = H; p.W = W; p.Q = Q; p.lat_ctot = lat_ctot; p.lat_coff = lat_coff;
   p.unfold9 = unfold9 ? 1 : 0; p.n_samp = n_samp; p.n_enc = n_enc;
-  p.lo = (float)(-1.0 + 1e-6); p.hi = (float)(1.0 - 1e-6);
-  p.c0y = (float)(-1.0 + 1.0 / H); p.sy = (float)(2.0 * (1.0 / H));
-  p.c0x = (float)(-1.0 + 1.0 / W); p.sx = (float)(2.0 * (1.0 / W));
+  p.lo = as::kCoordLo; p.hi = as::kCoordHi;
+  const as::CoordAxis ay = as::coord_axis(H), ax = as::coord_axis(W);
+  p.c0y = ay.c0; p.sy = ay.s; p.c0x = ax.c0; p.sx = ax.s;
   // liif.py:149-150,160-161: rx = 2/H/2 shifts the row, ry = 2/W/2 the column; the Python double `v*r + 1e-6` is rounded to
   // fp32 when it is added to the fp32 coordinate tensor
   const double ry_ = 2.0 / H / 2.0, rx_ = 2.0 / W / 2.0;
@@ -382,7 +380,7 @@ int as_convex_upsample_quater(const float* disp, const float* scale, const float
   AS_REQUIRE(B > 0 && H > 0 && W > 0 && Q > 0, AS_ERR_BAD_ARG, "convex_upsample_quater: non-positive size");
   const double ry = 2.0 / H / 2.0, rx = 2.0 / W / 2.0;  // submodule.py:383-384
   hipLaunchKernelGGL(convex_quater_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream),
-                     disp, scale, mask, coord, out, B, H, W, Q, mask_is_logits, (float)(-1.0 + 1e-6), (float)(1.0 - 1e-6),
+                     disp, scale, mask, coord, out, B, H, W, Q, mask_is_logits, as::kCoordLo, as::kCoordHi,
                      (float)(-ry + 1e-6), (float)(ry + 1e-6), (float)(-rx + 1e-6), (float)(rx + 1e-6));
   return as::check_launch("convex_upsample_quater");
 }
@@ -412,8 +410,8 @@ int as_convex_upsample_quater_bwd(const float* disp, const float* scale, const f
   }
   const double ry = 2.0 / H / 2.0, rx = 2.0 / W / 2.0;
   hipLaunchKernelGGL(convex_quater_bwd_kernel, dim3((unsigned)as::cdiv64((long long)B * Q, 256)), dim3(256), 0, as::as_stream(stream),
-                     disp, scale, mask, coord, d_out, d_mask, d_disp, B, H, W, Q, mask_is_logits, (float)(-1.0 + 1e-6),
-                     (float)(1.0 - 1e-6), (float)(-ry + 1e-6), (float)(ry + 1e-6), (float)(-rx + 1e-6), (float)(rx + 1e-6));
+                     disp, scale, mask, coord, d_out, d_mask, d_disp, B, H, W, Q, mask_is_logits, as::kCoordLo,
+                     as::kCoordHi, (float)(-ry + 1e-6), (float)(ry + 1e-6), (float)(-rx + 1e-6), (float)(rx + 1e-6));
   return as::check_launch("convex_upsample_quater_bwd");
 }
 

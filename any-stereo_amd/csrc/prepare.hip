@@ -22,6 +22,7 @@
 // this file.
 #include "common.h"
 #include "cubic.h"
+#include "query.h"
 
 #pragma clang fp contract(off)
 
@@ -147,9 +148,8 @@ __global__ __launch_bounds__(kThreads) void query_grid_kernel(float* __restrict_
 
 inline Axis make_axis(int n_hr, int lo, int n_crop, int n_want) {
   Axis a;
-  const double r = 2.0 / (2.0 * (double)n_hr);  // make_coord (liif.py:32-45): r = (v1 - v0) / (2 n), seq = v0 + r + (2 r) * arange(n)
-  a.c0 = (float)(-1.0 + r);
-  a.step = (float)(2.0 * r);
+  const as::CoordAxis hr = as::coord_axis(n_hr);  // make_coord of the high-res frame (query.h)
+  a.c0 = hr.c0; a.step = hr.s;
   a.lo = lo;
   a.n_crop = n_crop;
   a.scale = (float)n_crop / (float)n_want;

@@ -66,6 +66,7 @@ struct Scene {
 };
 
 // make_coord of one axis: value(i) = c0 + step * i with c0 = fl(-1 + 1/n), step = fl(2/n), both formed in double and rounded once
+// (stated in ../query.h, coord_axis: the same floats; restated because this library's source hash covers csrc/scenes/ alone)
 struct Axis {
   float c0, step;
 };

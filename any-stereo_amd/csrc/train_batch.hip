@@ -20,6 +20,7 @@
 // Every operation of the coordinate and the resize arithmetic is rounded on its own, as the torch ops it restates are: no FMA
 // contraction in this file.
 #include "common.h"
+#include "query.h"
 
 #include <math.h>
 
@@ -39,7 +40,7 @@ struct Sample {
   int* list;       // [n] valid pixels, then invalid pixels, both in raster order (sparse modes)
   int* tile_off;   // [tiles] valid pixels in front of a tile (count writes the tile's own count, scan makes it exclusive)
   int h, w, n, tiles;
-  float c0h, steph, c0w, stepw;   // make_coord: value(i) = c0 + step * i, c0 = fl(-1 + 1/n), step = fl(2/n)
+  float c0h, steph, c0w, stepw;   // make_coord (query.h: coord_axis): value(i) = c0 + step * i
   float scale;                    // copied to scale_out, so the batch's `scale` tensor needs no upload
   uint32_t key[kRounds];
 };
@@ -267,12 +268,6 @@ int check_sizes(const char* what, const int* h_hr, const int* w_hr, int B) {
   return AS_OK;
 }
 
-inline void coord_axis(int n, float& c0, float& step) {
-  const double r = 2.0 / (2.0 * (double)n);  // make_coord (stereo_datasets.py:27-28): r = (v1 - v0) / (2 n), seq = v0 + r + (2 r) * arange(n)
-  c0 = (float)(-1.0 + r);
-  step = (float)(2.0 * r);
-}
-
 }  // namespace
 
 extern "C" {
@@ -333,8 +328,8 @@ int as_train_queries(const float* const* crops, const int* h_hr, const int* w_hr
       e.w = w_hr[b];
       e.n = e.h * e.w;
       e.tiles = (int)as::cdiv64(e.n, kTile);
-      coord_axis(e.h, e.c0h, e.steph);
-      coord_axis(e.w, e.c0w, e.stepw);
+      const as::CoordAxis ah = as::coord_axis(e.h), aw = as::coord_axis(e.w);  // make_coord (stereo_datasets.py:27-28)
+      e.c0h = ah.c0; e.steph = ah.s; e.c0w = aw.c0; e.stepw = aw.s;
       derive_keys(seed, b, mode, e.key);
       e.scale = scale ? scale[b] : 0.f;
       if (sparse) {
