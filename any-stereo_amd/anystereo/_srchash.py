@@ -38,3 +38,20 @@ def scenes_source_hash() -> str | None:
             h.update(open(os.path.join(SCENES_CSRC, f), "rb").read())
     h.update(open(SCENES_HEADER, "rb").read())
     return h.hexdigest()[:16]
+
+
+AUGMENT_CSRC = os.path.join(CSRC, "augment")
+AUGMENT_HEADER = os.path.join(PKG, "..", "..", "include", "anystereo_augment.h")
+
+
+def augment_source_hash() -> str | None:
+    """The same for libanystereo_augment.so: csrc/augment/* and include/anystereo_augment.h only (`aug_source_hash()`)."""
+    if not (os.path.isdir(AUGMENT_CSRC) and os.path.exists(AUGMENT_HEADER)):
+        return None
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(AUGMENT_CSRC)):
+        if f.endswith((".hip", ".h")):
+            h.update(f.encode())
+            h.update(open(os.path.join(AUGMENT_CSRC, f), "rb").read())
+    h.update(open(AUGMENT_HEADER, "rb").read())
+    return h.hexdigest()[:16]

@@ -491,16 +491,22 @@ def scene_scales(seed: int, step: int, batch: int, scale_min: float, scale_max: 
 
 
 def scene_train_batch(spec: SceneSpec, seed: int, step: int, batch: int, h_lr: int = 160, w_lr: int = 320, scale_min: float = 1.0,
-                      scale_max: float = 2.95, mode: str = "dense", rank: int = 0, world: int = 1, device="cpu", low_disp: bool = True):
+                      scale_max: float = 2.95, mode: str = "dense", rank: int = 0, world: int = 1, device="cpu", low_disp: bool = True,
+                      augment=None):
     """`build_train_batch(...)`'s tuple (image1, image2, hr_coord, hr_disp, scale, low_disp) for step `step` of rank `rank`: fresh scenes
     (index = (step * world + rank) * batch + b) rendered at (h_lr, w_lr), one hashed scale per sample, ragged ground-truth crops
     rendered at (round(h_lr s), round(w_lr s)) in their own pixels, the queries drawn by `build_train_batch` with a seed of this
-    (step, rank).  On a CUDA device: four launches and no host synchronisation."""
+    (step, rank).  On a CUDA device: four launches and no host synchronisation.  `augment`: a `harness.augment.PhotoSpec` — the rendered
+    pair goes through the reference's photometric augmentation and eraser (parameters hashed per scene index) before the batch is
+    built: up to three more launches, ground truth and queries unchanged.  None (the default): nothing of that runs."""
     batch = int(batch)
     scales = scene_scales(seed, step, batch, scale_min, scale_max, rank, world)
     first = (int(step) * int(world) + int(rank)) * batch
     indices = [first + b for b in range(batch)]
     im1, im2 = render_pair(spec, seed, first, batch, h_lr, w_lr, device)
+    if augment is not None:
+        from .augment import augment_pair
+        im1, im2 = augment_pair(im1, im2, augment, seed, first)
     sizes = [(round(h_lr * s), round(w_lr * s)) for s in scales]
     disps, _, _ = ground_truth(spec, seed, sizes, indices, device, want=("disp",))
     return batches.build_train_batch(im1, im2, disps, scales, (int(seed) + int(step) * int(world) + int(rank)) & _M64, mode=mode,

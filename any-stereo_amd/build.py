@@ -1,4 +1,4 @@
-"""Build libanystereo_hip.so and libanystereo_scenes.so (gfx950 only) in-tree with hipcc.
+"""Build libanystereo_hip.so, libanystereo_scenes.so and libanystereo_augment.so (gfx950 only) in-tree with hipcc.
 
     python any-stereo_amd/build.py [--force]
 
@@ -91,6 +91,48 @@ def build_scenes(force: bool = False, verbose: bool = True) -> str:
     return SCENES_LIB
 
 
+# libanystereo_augment.so (include/anystereo_augment.h): the photometric augmentation's library, a build of its own like the scenes'
+AUGMENT_CSRC = os.path.join(CSRC, "augment")
+AUGMENT_OBJ = os.path.join(OBJ, "augment")
+AUGMENT_LIB = os.path.join(LIBDIR, "libanystereo_augment.so")
+AUGMENT_HEADER = os.path.join(HERE, "..", "include", "anystereo_augment.h")
+
+
+def build_augment(force: bool = False, verbose: bool = True) -> str:
+    """The recipe of `build_scenes` with the same flags: objects under build/augment/, the source hash compiled in
+    (`aug_source_hash`; `_augment_lib.load()` refuses a stale binary)."""
+    os.makedirs(AUGMENT_OBJ, exist_ok=True)
+    os.makedirs(LIBDIR, exist_ok=True)
+    srcs = sorted(f for f in os.listdir(AUGMENT_CSRC) if f.endswith(".hip"))
+    stamp_src = os.path.join(AUGMENT_OBJ, "stamp.cpp")
+    stamp = 'extern "C" const char* aug_source_hash(void) { return "%s"; }\n' % _srchash().augment_source_hash()
+    if not os.path.exists(stamp_src) or open(stamp_src).read() != stamp:
+        open(stamp_src, "w").write(stamp)
+    deps = [os.path.join(AUGMENT_CSRC, f) for f in sorted(os.listdir(AUGMENT_CSRC)) if f.endswith(".h")] + [AUGMENT_HEADER]
+    hipcc = _hipcc()
+    objs, compiled = [], False
+    for s in srcs:
+        src, obj = os.path.join(AUGMENT_CSRC, s), os.path.join(AUGMENT_OBJ, s[:-4] + ".o")
+        objs.append(obj)
+        if force or _newer([src] + deps, obj):
+            r = subprocess.run([hipcc] + FLAGS + ["-c", src, "-o", obj], capture_output=True, text=True)
+            if verbose and (r.stderr.strip() or r.returncode):
+                sys.stderr.write(r.stderr)
+            if r.returncode != 0:
+                raise RuntimeError(f"hipcc failed on {src}")
+            compiled = True
+            if verbose:
+                print(f"[build] compiled augment/{s}")
+    if force or compiled or _newer(objs + [stamp_src], AUGMENT_LIB):
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", AUGMENT_LIB] + objs + [stamp_src], capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr)
+            raise RuntimeError("link failed")
+        if verbose:
+            print(f"[build] linked {AUGMENT_LIB}")
+    return AUGMENT_LIB
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIBDIR, exist_ok=True)
@@ -134,6 +176,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
         if verbose:
             print(f"[build] linked {LIB}")
     build_scenes(force=force, verbose=verbose)
+    build_augment(force=force, verbose=verbose)
     return LIB
 
 

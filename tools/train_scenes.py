@@ -4,6 +4,7 @@ first run of this training stack on data whose ground truth has something to do 
     python tools/train_scenes.py --steps 200                       # 160 x 320, batch 4, 16 GRU iterations, split precision
     python tools/train_scenes.py --steps 20 --height 64 --width 128 --batch 2 --iters 4
     python tools/train_scenes.py --steps 50 --no-supervise-init --eager
+    python tools/train_scenes.py --steps 200 --augment flow        # the reference's photometric augmentation and eraser on every pair
 
 Every step draws `--batch` new scenes (`scene_train_batch`: the pair at the network's size, one hashed scale per sample in
 [--scale-min, --scale-max], the ground truth rendered at that scale's size, the queries drawn on the device).  Held-out: 8 scenes
@@ -45,6 +46,9 @@ def parse_args(argv=None):
     ap.add_argument("--no-supervise-init", action="store_true", help="train without the 1/4-resolution loss on init_disp (low_disp)")
     ap.add_argument("--eager", action="store_true", help="no captured step graph")
     ap.add_argument("--held-out", type=int, default=8)
+    ap.add_argument("--augment", default=None, choices=["flow", "sparse"],
+                    help="photometric augmentation and eraser of every training pair (harness/augment.py: FlowAugmentor's or "
+                         "SparseFlowAugmentor's constants); default: none")
     ap.add_argument("--eval-iters", type=int, default=None, help="GRU iterations of the held-out queries; default: --iters")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.batch < 1 or a.held_out < 1:
@@ -99,6 +103,10 @@ def main():
     fill_module_deterministic(model, base_seed=1)
     model = model.to(dev)
     supervise = not a.no_supervise_init and "IGEV" in a.model
+    photo = None
+    if a.augment is not None:
+        from anystereo.harness.augment import PhotoSpec
+        photo = getattr(PhotoSpec, a.augment)()
     eval_iters = a.eval_iters or a.iters
     before = held_out_epe(model, spec, a.seed, a.held_out, a.height, a.width, (1.0, 2.0), eval_iters, dev)
     tr = Trainer(model, lr=a.lr, num_steps=a.steps, train_iters=a.iters, max_disp=args.max_disp, supervise_init=supervise,
@@ -108,7 +116,7 @@ def main():
     t0 = time.perf_counter()
     for step in range(a.steps):
         batch = scene_train_batch(spec, a.seed, step, a.batch, a.height, a.width, a.scale_min, a.scale_max, mode="dense", device=dev,
-                                  low_disp=supervise)
+                                  low_disp=supervise, augment=photo)
         loss, _ = tr.step(batch)
         losses.append(loss.detach() if torch.is_tensor(loss) else torch.tensor(float(loss)))
     torch.cuda.synchronize()
@@ -118,7 +126,7 @@ def main():
     k = max(1, min(10, a.steps // 4))
     print(json.dumps({"tool": "train_scenes", "model": a.model, "steps": a.steps, "size": [a.height, a.width], "batch": a.batch,
                       "iters": a.iters, "eval_iters": eval_iters, "precision": a.precision, "supervise_init": supervise, "lr": a.lr,
-                      "graphed_step": bool(tr.use_graph), "scene_layers": spec.n_layers, "scales": [a.scale_min, a.scale_max],
+                      "graphed_step": bool(tr.use_graph), "scene_layers": spec.n_layers, "augment": a.augment, "scales": [a.scale_min, a.scale_max],
                       "weights": "deterministic fill", "loss_first": losses[0], "loss_last": losses[-1],
                       "loss_mean_first_k": sum(losses[:k]) / k, "loss_mean_last_k": sum(losses[-k:]) / k, "k": k,
                       "loss_every_10th": [round(v, 4) for v in losses[::10]], "finite": all(v == v and abs(v) != float("inf") for v in losses),
