@@ -55,3 +55,25 @@ def augment_source_hash() -> str | None:
             h.update(open(os.path.join(AUGMENT_CSRC, f), "rb").read())
     h.update(open(AUGMENT_HEADER, "rb").read())
     return h.hexdigest()[:16]
+
+
+SPATIAL_CSRC = os.path.join(CSRC, "spatial")
+SPATIAL_HEADER = os.path.join(PKG, "..", "..", "include", "anystereo_spatial.h")
+SPATIAL_SHARED = (os.path.join(CSRC, "cubic.h"),)   # top-level headers csrc/spatial/ includes: the final resize's arithmetic
+
+
+def spatial_source_hash() -> str | None:
+    """The same for libanystereo_spatial.so: csrc/spatial/*, include/anystereo_spatial.h and the one header it shares with the main
+    library, csrc/cubic.h (`spt_source_hash()`)."""
+    if not (os.path.isdir(SPATIAL_CSRC) and os.path.exists(SPATIAL_HEADER) and all(os.path.exists(f) for f in SPATIAL_SHARED)):
+        return None
+    h = hashlib.sha256()
+    for f in sorted(os.listdir(SPATIAL_CSRC)):
+        if f.endswith((".hip", ".h")):
+            h.update(f.encode())
+            h.update(open(os.path.join(SPATIAL_CSRC, f), "rb").read())
+    for f in SPATIAL_SHARED:
+        h.update(os.path.basename(f).encode())
+        h.update(open(f, "rb").read())
+    h.update(open(SPATIAL_HEADER, "rb").read())
+    return h.hexdigest()[:16]

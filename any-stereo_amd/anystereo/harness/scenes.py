@@ -492,17 +492,38 @@ def scene_scales(seed: int, step: int, batch: int, scale_min: float, scale_max: 
 
 def scene_train_batch(spec: SceneSpec, seed: int, step: int, batch: int, h_lr: int = 160, w_lr: int = 320, scale_min: float = 1.0,
                       scale_max: float = 2.95, mode: str = "dense", rank: int = 0, world: int = 1, device="cpu", low_disp: bool = True,
-                      augment=None):
+                      augment=None, spatial=None, frame_hw=None):
     """`build_train_batch(...)`'s tuple (image1, image2, hr_coord, hr_disp, scale, low_disp) for step `step` of rank `rank`: fresh scenes
     (index = (step * world + rank) * batch + b) rendered at (h_lr, w_lr), one hashed scale per sample, ragged ground-truth crops
     rendered at (round(h_lr s), round(w_lr s)) in their own pixels, the queries drawn by `build_train_batch` with a seed of this
     (step, rank).  On a CUDA device: four launches and no host synchronisation.  `augment`: a `harness.augment.PhotoSpec` — the rendered
     pair goes through the reference's photometric augmentation and eraser (parameters hashed per scene index) before the batch is
-    built: up to three more launches, ground truth and queries unchanged.  None (the default): nothing of that runs."""
+    built: up to three more launches, ground truth and queries unchanged.  None (the default): nothing of that runs.
+    `spatial`: a `harness.spatial.SpatialSpec` — the scenes are rendered as full frames of `frame_hw` (default 540 x 960) with full-frame
+    ground truth and go through `harness.spatial.augment_frames`, the reference's whole `*WoCrop.__call__`: `augment` (if given), then
+    rescale / flip / crop to (round(h_lr s), round(w_lr s)) and the final resize of the images to (h_lr, w_lr); a sparse spec takes the
+    scenes' exact non-occlusion mask as `valid`, and the returned disparity crops are set to 0 wherever the returned validity is 0,
+    so that `build_train_batch(mode="sparse")`, which reads validity as disp > 0, sees the same pixels valid in rescaled and in
+    passed-through samples (a passed-through occluded pixel keeps a positive disparity otherwise).  A sparse spec with
+    do_flip="hf" yields negative disparities, as the reference's: no pixel of a flipped sample is valid to that mode.  None (the default): nothing of that runs and the outputs are what they were."""
     batch = int(batch)
     scales = scene_scales(seed, step, batch, scale_min, scale_max, rank, world)
     first = (int(step) * int(world) + int(rank)) * batch
     indices = [first + b for b in range(batch)]
+    if spatial is not None:
+        from .spatial import augment_frames
+        fh, fw = (540, 960) if frame_hw is None else (int(frame_hw[0]), int(frame_hw[1]))
+        im1, im2 = render_pair(spec, seed, first, batch, fh, fw, device)
+        sparse = spatial.kind == "sparse"
+        full, _, noc = ground_truth(spec, seed, [(fh, fw)] * batch, indices, device, want=("disp", "noc") if sparse else ("disp",))
+        im1, im2, disps, valids = augment_frames(im1, im2, torch.stack(full), augment, spatial, seed, first, scales, (h_lr, w_lr),
+                                                 valid=torch.stack(noc) if sparse else None)
+        if sparse:
+            disps = [torch.where(v != 0, d, torch.zeros_like(d)) for d, v in zip(disps, valids)]
+        return batches.build_train_batch(im1, im2, disps, scales, (int(seed) + int(step) * int(world) + int(rank)) & _M64, mode=mode,
+                                         low_disp=low_disp)
+    if frame_hw is not None:
+        raise ValueError("scene_train_batch: frame_hw is the frame of the spatial augmentation; it needs `spatial`")
     im1, im2 = render_pair(spec, seed, first, batch, h_lr, w_lr, device)
     if augment is not None:
         from .augment import augment_pair

@@ -1,4 +1,4 @@
-"""Build libanystereo_hip.so, libanystereo_scenes.so and libanystereo_augment.so (gfx950 only) in-tree with hipcc.
+"""Build libanystereo_hip.so, libanystereo_scenes.so, libanystereo_augment.so and libanystereo_spatial.so (gfx950 only) in-tree with hipcc.
 
     python any-stereo_amd/build.py [--force]
 
@@ -133,6 +133,50 @@ def build_augment(force: bool = False, verbose: bool = True) -> str:
     return AUGMENT_LIB
 
 
+# libanystereo_spatial.so (include/anystereo_spatial.h): the spatial augmentation's library, a build of its own like the two above; it
+# includes csrc/cubic.h, which is therefore one of its dependencies and part of its source hash
+SPATIAL_CSRC = os.path.join(CSRC, "spatial")
+SPATIAL_OBJ = os.path.join(OBJ, "spatial")
+SPATIAL_LIB = os.path.join(LIBDIR, "libanystereo_spatial.so")
+SPATIAL_HEADER = os.path.join(HERE, "..", "include", "anystereo_spatial.h")
+
+
+def build_spatial(force: bool = False, verbose: bool = True) -> str:
+    """The recipe of `build_augment`: objects under build/spatial/, the source hash compiled in (`spt_source_hash`;
+    `_spatial_lib.load()` refuses a stale binary)."""
+    os.makedirs(SPATIAL_OBJ, exist_ok=True)
+    os.makedirs(LIBDIR, exist_ok=True)
+    srcs = sorted(f for f in os.listdir(SPATIAL_CSRC) if f.endswith(".hip"))
+    stamp_src = os.path.join(SPATIAL_OBJ, "stamp.cpp")
+    stamp = 'extern "C" const char* spt_source_hash(void) { return "%s"; }\n' % _srchash().spatial_source_hash()
+    if not os.path.exists(stamp_src) or open(stamp_src).read() != stamp:
+        open(stamp_src, "w").write(stamp)
+    deps = ([os.path.join(SPATIAL_CSRC, f) for f in sorted(os.listdir(SPATIAL_CSRC)) if f.endswith(".h")] + [SPATIAL_HEADER]
+            + list(_srchash().SPATIAL_SHARED))
+    hipcc = _hipcc()
+    objs, compiled = [], False
+    for s in srcs:
+        src, obj = os.path.join(SPATIAL_CSRC, s), os.path.join(SPATIAL_OBJ, s[:-4] + ".o")
+        objs.append(obj)
+        if force or _newer([src] + deps, obj):
+            r = subprocess.run([hipcc] + FLAGS + ["-c", src, "-o", obj], capture_output=True, text=True)
+            if verbose and (r.stderr.strip() or r.returncode):
+                sys.stderr.write(r.stderr)
+            if r.returncode != 0:
+                raise RuntimeError(f"hipcc failed on {src}")
+            compiled = True
+            if verbose:
+                print(f"[build] compiled spatial/{s}")
+    if force or compiled or _newer(objs + [stamp_src], SPATIAL_LIB):
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", SPATIAL_LIB] + objs + [stamp_src], capture_output=True, text=True)
+        if r.returncode != 0:
+            sys.stderr.write(r.stderr)
+            raise RuntimeError("link failed")
+        if verbose:
+            print(f"[build] linked {SPATIAL_LIB}")
+    return SPATIAL_LIB
+
+
 def build(force: bool = False, verbose: bool = True) -> str:
     os.makedirs(OBJ, exist_ok=True)
     os.makedirs(LIBDIR, exist_ok=True)
@@ -177,6 +221,7 @@ def build(force: bool = False, verbose: bool = True) -> str:
             print(f"[build] linked {LIB}")
     build_scenes(force=force, verbose=verbose)
     build_augment(force=force, verbose=verbose)
+    build_spatial(force=force, verbose=verbose)
     return LIB
 
 

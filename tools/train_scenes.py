@@ -5,6 +5,7 @@ first run of this training stack on data whose ground truth has something to do 
     python tools/train_scenes.py --steps 20 --height 64 --width 128 --batch 2 --iters 4
     python tools/train_scenes.py --steps 50 --no-supervise-init --eager
     python tools/train_scenes.py --steps 200 --augment flow        # the reference's photometric augmentation and eraser on every pair
+    python tools/train_scenes.py --steps 200 --augment flow --spatial flow --frame 540 960    # ... and its rescale / flip / crop / resize
 
 Every step draws `--batch` new scenes (`scene_train_batch`: the pair at the network's size, one hashed scale per sample in
 [--scale-min, --scale-max], the ground truth rendered at that scale's size, the queries drawn on the device).  Held-out: 8 scenes
@@ -49,10 +50,16 @@ def parse_args(argv=None):
     ap.add_argument("--augment", default=None, choices=["flow", "sparse"],
                     help="photometric augmentation and eraser of every training pair (harness/augment.py: FlowAugmentor's or "
                          "SparseFlowAugmentor's constants); default: none")
+    ap.add_argument("--spatial", default=None, choices=["flow", "sparse"],
+                    help="spatial augmentation (harness/spatial.py: FlowAugmentorWoCrop's or SparseFlowAugmentorWoCrop's constants): the scenes "
+                         "are rendered as --frame frames, rescaled, cropped and resized to --height x --width; default: none")
+    ap.add_argument("--frame", type=int, nargs=2, default=None, metavar=("H", "W"), help="the full frame of --spatial; default 540 960")
     ap.add_argument("--eval-iters", type=int, default=None, help="GRU iterations of the held-out queries; default: --iters")
     a = ap.parse_args(argv)
     if a.steps < 1 or a.batch < 1 or a.held_out < 1:
         ap.error("--steps, --batch and --held-out must be positive")
+    if a.frame is not None and a.spatial is None:
+        ap.error("--frame needs --spatial")
     return a
 
 
@@ -107,6 +114,10 @@ def main():
     if a.augment is not None:
         from anystereo.harness.augment import PhotoSpec
         photo = getattr(PhotoSpec, a.augment)()
+    spatial = None
+    if a.spatial is not None:
+        from anystereo.harness.spatial import SpatialSpec
+        spatial = SpatialSpec.flow() if a.spatial == "flow" else SpatialSpec.sparse(wo_crop=True)
     eval_iters = a.eval_iters or a.iters
     before = held_out_epe(model, spec, a.seed, a.held_out, a.height, a.width, (1.0, 2.0), eval_iters, dev)
     tr = Trainer(model, lr=a.lr, num_steps=a.steps, train_iters=a.iters, max_disp=args.max_disp, supervise_init=supervise,
@@ -115,8 +126,9 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for step in range(a.steps):
-        batch = scene_train_batch(spec, a.seed, step, a.batch, a.height, a.width, a.scale_min, a.scale_max, mode="dense", device=dev,
-                                  low_disp=supervise, augment=photo)
+        batch = scene_train_batch(spec, a.seed, step, a.batch, a.height, a.width, a.scale_min, a.scale_max,
+                                  mode="sparse" if a.spatial == "sparse" else "dense",   # a sparse ground truth: the sparse query draw
+                                  device=dev, low_disp=supervise, augment=photo, spatial=spatial, frame_hw=a.frame)
         loss, _ = tr.step(batch)
         losses.append(loss.detach() if torch.is_tensor(loss) else torch.tensor(float(loss)))
     torch.cuda.synchronize()
@@ -126,7 +138,8 @@ def main():
     k = max(1, min(10, a.steps // 4))
     print(json.dumps({"tool": "train_scenes", "model": a.model, "steps": a.steps, "size": [a.height, a.width], "batch": a.batch,
                       "iters": a.iters, "eval_iters": eval_iters, "precision": a.precision, "supervise_init": supervise, "lr": a.lr,
-                      "graphed_step": bool(tr.use_graph), "scene_layers": spec.n_layers, "augment": a.augment, "scales": [a.scale_min, a.scale_max],
+                      "graphed_step": bool(tr.use_graph), "scene_layers": spec.n_layers, "augment": a.augment, "spatial": a.spatial, "frame": a.frame,
+                      "scales": [a.scale_min, a.scale_max],
                       "weights": "deterministic fill", "loss_first": losses[0], "loss_last": losses[-1],
                       "loss_mean_first_k": sum(losses[:k]) / k, "loss_mean_last_k": sum(losses[-k:]) / k, "k": k,
                       "loss_every_10th": [round(v, 4) for v in losses[::10]], "finite": all(v == v and abs(v) != float("inf") for v in losses),
