@@ -206,7 +206,7 @@ def load() -> C.CDLL:
         fn.restype = res
         fn.argtypes = args
     from ._srchash import source_hash
-    want, have = source_hash(), lib.as_source_hash().decode()
+    want, have = source_hash("hip"), lib.as_source_hash().decode()
     if want is not None and want != have and os.environ.get("ANYSTEREO_ALLOW_STALE_LIB", "0") != "1":
         raise RuntimeError(f"{LIB_PATH} was built from other sources (library {have}, tree {want}): run `python any-stereo_amd/build.py` "
                            "(ANYSTEREO_ALLOW_STALE_LIB=1 overrides)")
@@ -218,7 +218,7 @@ def library_info() -> dict:
     """What is loaded: path, ABI version, the source hash compiled into it and whether it matches the tree."""
     from ._srchash import source_hash
     lib = load()
-    have, want = lib.as_source_hash().decode(), source_hash()
+    have, want = lib.as_source_hash().decode(), source_hash("hip")
     return {"path": os.path.relpath(LIB_PATH), "abi": int(lib.as_abi_version()), "src_hash": have,
             "matches_sources": None if want is None else have == want}
 

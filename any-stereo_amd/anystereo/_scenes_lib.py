@@ -1,15 +1,16 @@
 """ctypes binding of libanystereo_scenes.so (C ABI: include/anystereo_scenes.h): the procedural scenes' library.
 
-Modelled on `_lib.py`: every declared symbol is bound at load, a library built from other sources is refused, and there is no
-fallback — `harness.scenes` calls the host restatements for CPU tensors because they are CPU tensors, never because a kernel is
-missing.
+Loaded like `_lib.py`, by `_native.open_library`: every declared symbol is bound at load, a library built from other sources is
+refused, and there is no fallback — `harness.scenes` calls the host restatements for CPU tensors because they are CPU tensors,
+never because a kernel is missing.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch  # noqa: F401  (pins the HIP runtime this library binds to, as in _lib.py)
+
+from . import _native
 
 SCN_MAX_LAYERS = 8
 SCN_MAX_OCTAVES = 6
@@ -18,7 +19,7 @@ SCN_LAYER_FLOATS = 16
 SCN_OK, SCN_ERR_BAD_ARG, SCN_ERR_BAD_SHAPE, SCN_ERR_LAUNCH = 0, -1, -2, -3
 KIND_PLANE, KIND_ELLIPSE, KIND_PARALLELOGRAM = 0, 1, 2
 
-LIB_PATH = os.environ.get("ANYSTEREO_SCENES_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanystereo_scenes.so")
+LIB_PATH = _native.lib_path("scenes")
 
 _vp, _i = C.c_void_p, C.c_int
 
@@ -54,34 +55,15 @@ _lib = None
 def load() -> C.CDLL:
     """Load the library (once) and bind every declared symbol; raises if anything is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"libanystereo_scenes.so not found at {LIB_PATH}: build it with `python any-stereo_amd/build.py` "
-                           "(or __graft_entry__.build()).")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    from ._srchash import scenes_source_hash
-    want, have = scenes_source_hash(), lib.scn_source_hash().decode()
-    if want is not None and want != have and os.environ.get("ANYSTEREO_ALLOW_STALE_LIB", "0") != "1":
-        raise RuntimeError(f"{LIB_PATH} was built from other sources (library {have}, tree {want}): run `python any-stereo_amd/build.py` "
-                           "(ANYSTEREO_ALLOW_STALE_LIB=1 overrides)")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _native.open_library("scenes", SIGNATURES, LIB_PATH)
+    return _lib
 
 
 def library_info() -> dict:
-    from ._srchash import scenes_source_hash
-    lib = load()
-    have, want = lib.scn_source_hash().decode(), scenes_source_hash()
-    return {"path": os.path.relpath(LIB_PATH), "abi": int(lib.scn_abi_version()), "src_hash": have,
-            "matches_sources": None if want is None else have == want}
+    return _native.library_info("scenes", load())
 
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        msg = load().scn_last_error_string().decode("utf-8", "replace")
-        raise RuntimeError(f"anystereo scenes call {what} failed (code {rc}): {msg}")
+        _native.raise_for("scenes", rc, what, load())

@@ -1,15 +1,16 @@
 """ctypes binding of libanystereo_spatial.so (C ABI: include/anystereo_spatial.h): the spatial augmentation's library.
 
-Modelled on `_augment_lib.py`: every declared symbol is bound at load, a library built from other sources is refused, and there is
-no fallback — `harness.spatial` calls the host restatement for CPU tensors because they are CPU tensors, never because a kernel
-is missing.
+Loaded like `_lib.py`, by `_native.open_library`: every declared symbol is bound at load, a library built from other sources is
+refused, and there is no fallback — `harness.spatial` calls the host restatement for CPU tensors because they are CPU tensors,
+never because a kernel is missing.
 """
 from __future__ import annotations
 
 import ctypes as C
-import os
 
 import torch  # noqa: F401  (pins the HIP runtime this library binds to, as in _lib.py)
+
+from . import _native
 
 SPT_MAX_BATCH = 8
 SPT_MIN_SCALE, SPT_MAX_SCALE = 0.125, 8.0
@@ -17,7 +18,7 @@ SPT_OK, SPT_ERR_BAD_ARG, SPT_ERR_BAD_SHAPE, SPT_ERR_LAUNCH, SPT_ERR_CROP, SPT_ER
 SPT_U8, SPT_F32 = 0, 1
 SPT_FLIP_NONE, SPT_FLIP_HF, SPT_FLIP_H, SPT_FLIP_V = 0, 1, 2, 3
 
-LIB_PATH = os.environ.get("ANYSTEREO_SPATIAL_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), "lib", "libanystereo_spatial.so")
+LIB_PATH = _native.lib_path("spatial")
 
 _vp, _i, _d = C.c_void_p, C.c_int, C.c_double
 
@@ -46,34 +47,15 @@ _lib = None
 def load() -> C.CDLL:
     """Load the library (once) and bind every declared symbol; raises if anything is missing."""
     global _lib
-    if _lib is not None:
-        return _lib
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError(f"libanystereo_spatial.so not found at {LIB_PATH}: build it with `python any-stereo_amd/build.py` "
-                           "(or __graft_entry__.build()).")
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)  # AttributeError if the symbol is not exported
-        fn.restype = res
-        fn.argtypes = args
-    from ._srchash import spatial_source_hash
-    want, have = spatial_source_hash(), lib.spt_source_hash().decode()
-    if want is not None and want != have and os.environ.get("ANYSTEREO_ALLOW_STALE_LIB", "0") != "1":
-        raise RuntimeError(f"{LIB_PATH} was built from other sources (library {have}, tree {want}): run `python any-stereo_amd/build.py` "
-                           "(ANYSTEREO_ALLOW_STALE_LIB=1 overrides)")
-    _lib = lib
-    return lib
+    if _lib is None:
+        _lib = _native.open_library("spatial", SIGNATURES, LIB_PATH)
+    return _lib
 
 
 def library_info() -> dict:
-    from ._srchash import spatial_source_hash
-    lib = load()
-    have, want = lib.spt_source_hash().decode(), spatial_source_hash()
-    return {"path": os.path.relpath(LIB_PATH), "abi": int(lib.spt_abi_version()), "src_hash": have,
-            "matches_sources": None if want is None else have == want}
+    return _native.library_info("spatial", load())
 
 
 def check(rc: int, what: str) -> None:
     if rc != 0:
-        msg = load().spt_last_error_string().decode("utf-8", "replace")
-        raise RuntimeError(f"anystereo spatial call {what} failed (code {rc}): {msg}")
+        _native.raise_for("spatial", rc, what, load())

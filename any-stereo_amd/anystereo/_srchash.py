@@ -1,79 +1,49 @@
-"""Content hash of the native sources (csrc/*.hip, csrc/*.h, include/anystereo_hip.h).  build.py compiles it into the library
-(`as_source_hash()`), `_lib.load()` recomputes it from the tree and refuses a library built from other sources: the built `.so`
-is git-ignored but travels with the repo snapshot, so a stale binary would otherwise run silently on the GPU box."""
+"""The table of the native libraries and the content hash of each one's sources.
+
+build.py compiles `source_hash(key)` into the library (`<prefix>_source_hash()`), `_native.open_library` recomputes it from the
+tree and refuses a library built from other sources: the built `.so` is git-ignored but travels with the repo snapshot, so a stale
+binary would otherwise run silently on the GPU box.  Each library has a hash of its own: the sources are the TOP LEVEL of its
+directory, so csrc/scenes/ is no part of the main library's hash, and an edit there rebuilds the scenes' library alone.
+
+build.py loads this file by path, without importing the package: nothing here imports anystereo or torch.
+"""
+import collections
 import hashlib
 import os
 
-PKG = os.path.dirname(os.path.abspath(__file__))
-CSRC = os.path.join(PKG, "..", "csrc")
-HEADER = os.path.join(PKG, "..", "..", "include", "anystereo_hip.h")
+ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..")   # the repository
+ERRSTATE = "any-stereo_amd/csrc/host/errstate.h"   # err_buf / fail / REQUIRE / check_launch of the three small libraries
+
+# file: in anystereo/lib/; sources, header, shared: paths below the repository root; shared: headers from outside `sources` that
+# its files include; prefix: of every exported symbol; override: the environment variable that names another build of the file
+Library = collections.namedtuple("Library", "file sources header shared prefix override")
+LIBRARIES = {
+    "hip": Library("libanystereo_hip.so", "any-stereo_amd/csrc", "include/anystereo_hip.h", (), "as", "ANYSTEREO_LIB"),
+    "scenes": Library("libanystereo_scenes.so", "any-stereo_amd/csrc/scenes", "include/anystereo_scenes.h", (ERRSTATE,), "scn",
+                      "ANYSTEREO_SCENES_LIB"),
+    "augment": Library("libanystereo_augment.so", "any-stereo_amd/csrc/augment", "include/anystereo_augment.h", (ERRSTATE,), "aug",
+                       "ANYSTEREO_AUGMENT_LIB"),
+    # cubic.h: the final resize's arithmetic, shared with the main library
+    "spatial": Library("libanystereo_spatial.so", "any-stereo_amd/csrc/spatial", "include/anystereo_spatial.h",
+                       ("any-stereo_amd/csrc/cubic.h", ERRSTATE), "spt", "ANYSTEREO_SPATIAL_LIB"),
+}
 
 
-def source_hash() -> str | None:
-    """None when the sources are not there (an installed library without its tree)."""
-    if not (os.path.isdir(CSRC) and os.path.exists(HEADER)):
+def source_hash(key: str, root: str = ROOT) -> str | None:
+    """16 hex digits over the *.hip and *.h files in the top level of the library's directory (sorted; name, then bytes), its shared
+    headers in the table's order (base name, then bytes) and its header's bytes.  None when any of them is not there (an installed
+    library without its tree)."""
+    lib = LIBRARIES[key]
+    csrc, header, shared = (os.path.join(root, lib.sources), os.path.join(root, lib.header), [os.path.join(root, f) for f in lib.shared])
+    if not (os.path.isdir(csrc) and all(os.path.exists(f) for f in [header] + shared)):
         return None
     h = hashlib.sha256()
-    for f in sorted(os.listdir(CSRC)):
+    for f in sorted(os.listdir(csrc)):
         if f.endswith((".hip", ".h")):
             h.update(f.encode())
-            h.update(open(os.path.join(CSRC, f), "rb").read())
-    h.update(open(HEADER, "rb").read())
-    return h.hexdigest()[:16]
-
-
-SCENES_CSRC = os.path.join(CSRC, "scenes")
-SCENES_HEADER = os.path.join(PKG, "..", "..", "include", "anystereo_scenes.h")
-
-
-def scenes_source_hash() -> str | None:
-    """The same for libanystereo_scenes.so: csrc/scenes/* and include/anystereo_scenes.h (`scn_source_hash()`).  `source_hash()` above
-    lists the top level of csrc/ only, so the scene sources are no part of the main library's hash."""
-    if not (os.path.isdir(SCENES_CSRC) and os.path.exists(SCENES_HEADER)):
-        return None
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(SCENES_CSRC)):
-        if f.endswith((".hip", ".h")):
-            h.update(f.encode())
-            h.update(open(os.path.join(SCENES_CSRC, f), "rb").read())
-    h.update(open(SCENES_HEADER, "rb").read())
-    return h.hexdigest()[:16]
-
-
-AUGMENT_CSRC = os.path.join(CSRC, "augment")
-AUGMENT_HEADER = os.path.join(PKG, "..", "..", "include", "anystereo_augment.h")
-
-
-def augment_source_hash() -> str | None:
-    """The same for libanystereo_augment.so: csrc/augment/* and include/anystereo_augment.h only (`aug_source_hash()`)."""
-    if not (os.path.isdir(AUGMENT_CSRC) and os.path.exists(AUGMENT_HEADER)):
-        return None
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(AUGMENT_CSRC)):
-        if f.endswith((".hip", ".h")):
-            h.update(f.encode())
-            h.update(open(os.path.join(AUGMENT_CSRC, f), "rb").read())
-    h.update(open(AUGMENT_HEADER, "rb").read())
-    return h.hexdigest()[:16]
-
-
-SPATIAL_CSRC = os.path.join(CSRC, "spatial")
-SPATIAL_HEADER = os.path.join(PKG, "..", "..", "include", "anystereo_spatial.h")
-SPATIAL_SHARED = (os.path.join(CSRC, "cubic.h"),)   # top-level headers csrc/spatial/ includes: the final resize's arithmetic
-
-
-def spatial_source_hash() -> str | None:
-    """The same for libanystereo_spatial.so: csrc/spatial/*, include/anystereo_spatial.h and the one header it shares with the main
-    library, csrc/cubic.h (`spt_source_hash()`)."""
-    if not (os.path.isdir(SPATIAL_CSRC) and os.path.exists(SPATIAL_HEADER) and all(os.path.exists(f) for f in SPATIAL_SHARED)):
-        return None
-    h = hashlib.sha256()
-    for f in sorted(os.listdir(SPATIAL_CSRC)):
-        if f.endswith((".hip", ".h")):
-            h.update(f.encode())
-            h.update(open(os.path.join(SPATIAL_CSRC, f), "rb").read())
-    for f in SPATIAL_SHARED:
+            h.update(open(os.path.join(csrc, f), "rb").read())
+    for f in shared:
         h.update(os.path.basename(f).encode())
         h.update(open(f, "rb").read())
-    h.update(open(SPATIAL_HEADER, "rb").read())
+    h.update(open(header, "rb").read())
     return h.hexdigest()[:16]

@@ -19,11 +19,11 @@
 // (correctly rounded whatever the fp32 division expands to).  anystereo/harness/augment.py restates every function below.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../../include/anystereo_augment.h"
+#include "../host/errstate.h"
 
 #pragma clang fp contract(off)
 
@@ -33,24 +33,6 @@ constexpr int kThreads = 256;
 constexpr int kPer = 8;  // pixels of a thread per tile
 static_assert(kThreads * kPer == AUG_TILE, "AUG_TILE is one block iteration");
 typedef unsigned long long u64;
-
-char* err_buf() {
-  static thread_local char buf[512] = "ok";
-  return buf;
-}
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(err_buf(), 512, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define AUG_REQUIRE(cond, code, ...)               \
-  do {                                             \
-    if (!(cond)) return fail(code, __VA_ARGS__);   \
-  } while (0)
 
 struct Table {
   aug_sample s[AUG_MAX_BATCH];
@@ -325,12 +307,6 @@ inline bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
   return a0 < b0 + (uintptr_t)nb && b0 < a0 + (uintptr_t)na;
 }
 
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(AUG_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-  return AUG_OK;
-}
-
 // 3 * B * h * w, saturated at 2^31 (no intermediate leaves int64)
 inline int64_t elements(int B, int h, int w) {
   const int64_t lim = 1ll << 31, hw = (int64_t)h * w;
@@ -346,16 +322,16 @@ inline int parts_of(int h, int w) {
 int check_image_params(int b, int img, const aug_image_params& P) {
   int seen = 0;
   for (int o = 0; o < 4; ++o) {
-    AUG_REQUIRE(P.order[o] >= 0 && P.order[o] <= 3 && !(seen & (1 << P.order[o])), AUG_ERR_BAD_ARG,
-                "aug_photometric_pair: sample %d image %d: order = (%d, %d, %d, %d) is no permutation of 0..3", b, img + 1, P.order[0], P.order[1],
-                P.order[2], P.order[3]);
+    REQUIRE(P.order[o] >= 0 && P.order[o] <= 3 && !(seen & (1 << P.order[o])), AUG_ERR_BAD_ARG,
+            "aug_photometric_pair: sample %d image %d: order = (%d, %d, %d, %d) is no permutation of 0..3", b, img + 1, P.order[0], P.order[1],
+            P.order[2], P.order[3]);
     seen |= 1 << P.order[o];
   }
   for (int k = 0; k < 3; ++k)
-    AUG_REQUIRE(isfinite(P.factor[k]) && P.factor[k] >= 0.f, AUG_ERR_BAD_ARG, "aug_photometric_pair: sample %d image %d: factor %d = %g must be finite and >= 0", b,
-                img + 1, k, (double)P.factor[k]);
-  AUG_REQUIRE(P.hue_shift >= 0 && P.hue_shift <= 255, AUG_ERR_BAD_ARG, "aug_photometric_pair: sample %d image %d: hue_shift = %d outside 0..255", b, img + 1,
-              P.hue_shift);
+    REQUIRE(isfinite(P.factor[k]) && P.factor[k] >= 0.f, AUG_ERR_BAD_ARG, "aug_photometric_pair: sample %d image %d: factor %d = %g must be finite and >= 0", b,
+            img + 1, k, (double)P.factor[k]);
+  REQUIRE(P.hue_shift >= 0 && P.hue_shift <= 255, AUG_ERR_BAD_ARG, "aug_photometric_pair: sample %d image %d: hue_shift = %d outside 0..255", b, img + 1,
+          P.hue_shift);
   return AUG_OK;
 }
 
@@ -386,15 +362,15 @@ int launch_chunks(const TIn* in1, const TIn* in2, TOut* out1, TOut* out2, int B,
     const dim3 grid((unsigned)parts, 2u, (unsigned)nb);
     if (any_contrast) {
       hipLaunchKernelGGL((grey_kernel<TIn>), grid, dim3(kThreads), 0, stream, t, in1 + off, in2 + off, wsb, n, tiles);
-      if (int rc = check_launch("aug_photometric_pair (grey sums)")) return rc;
+      if (int rc = check_launch("aug_photometric_pair (grey sums)", AUG_ERR_LAUNCH)) return rc;
     }
     hipLaunchKernelGGL((write_kernel<TIn, TOut>), grid, dim3(kThreads), 0, stream, t, in1 + off, in2 + off, out1 + off, out2 + off, lutb, wsb, n, tiles);
-    if (int rc = check_launch("aug_photometric_pair (write-out)")) return rc;
+    if (int rc = check_launch("aug_photometric_pair (write-out)", AUG_ERR_LAUNCH)) return rc;
     if (most > 0) {
       int64_t gx = (most + kThreads - 1) / kThreads;
       if (gx > 256) gx = 256;
       hipLaunchKernelGGL((rect_kernel<TOut>), dim3((unsigned)gx, AUG_MAX_RECTS, (unsigned)nb), dim3(kThreads), 0, stream, t, out2 + off, wsb, h, w, parts);
-      if (int rc = check_launch("aug_photometric_pair (rectangles)")) return rc;
+      if (int rc = check_launch("aug_photometric_pair (rectangles)", AUG_ERR_LAUNCH)) return rc;
     }
   }
   return AUG_OK;
@@ -416,41 +392,41 @@ int64_t aug_workspace_bytes(int B, int h, int w) {
 int aug_photometric_pair(const void* image1, const void* image2, int in_dtype, void* out1, void* out2, int out_dtype, int B, int h, int w,
                          const aug_sample* samples, const unsigned char* gamma_lut, void* workspace, int64_t workspace_bytes, void* stream) {
   const char* what = "aug_photometric_pair";
-  AUG_REQUIRE(image1 != nullptr && image2 != nullptr && out1 != nullptr && out2 != nullptr && samples != nullptr && workspace != nullptr, AUG_ERR_BAD_ARG,
-              "%s: null pointer", what);
-  AUG_REQUIRE((in_dtype == AUG_U8 || in_dtype == AUG_F32) && (out_dtype == AUG_U8 || out_dtype == AUG_F32), AUG_ERR_BAD_ARG,
-              "%s: in_dtype=%d out_dtype=%d: AUG_U8 or AUG_F32 expected", what, in_dtype, out_dtype);
-  AUG_REQUIRE(B >= 1 && h >= 1 && w >= 1, AUG_ERR_BAD_ARG, "%s: B=%d h=%d w=%d must be positive", what, B, h, w);
-  AUG_REQUIRE(elements(B, h, w) < (1ll << 31), AUG_ERR_BAD_SHAPE, "%s: B=%d h=%d w=%d: need 3*B*h*w < 2^31", what, B, h, w);
-  AUG_REQUIRE(in_dtype == AUG_U8 || (aligned(image1, 4) && aligned(image2, 4)), AUG_ERR_BAD_ARG, "%s: fp32 inputs must be 4-byte aligned", what);
-  AUG_REQUIRE(out_dtype == AUG_U8 || (aligned(out1, 4) && aligned(out2, 4)), AUG_ERR_BAD_ARG, "%s: fp32 outputs must be 4-byte aligned", what);
-  AUG_REQUIRE(aligned(workspace, 8), AUG_ERR_BAD_ARG, "%s: the workspace must be 8-byte aligned", what);
+  REQUIRE(image1 != nullptr && image2 != nullptr && out1 != nullptr && out2 != nullptr && samples != nullptr && workspace != nullptr, AUG_ERR_BAD_ARG,
+          "%s: null pointer", what);
+  REQUIRE((in_dtype == AUG_U8 || in_dtype == AUG_F32) && (out_dtype == AUG_U8 || out_dtype == AUG_F32), AUG_ERR_BAD_ARG,
+          "%s: in_dtype=%d out_dtype=%d: AUG_U8 or AUG_F32 expected", what, in_dtype, out_dtype);
+  REQUIRE(B >= 1 && h >= 1 && w >= 1, AUG_ERR_BAD_ARG, "%s: B=%d h=%d w=%d must be positive", what, B, h, w);
+  REQUIRE(elements(B, h, w) < (1ll << 31), AUG_ERR_BAD_SHAPE, "%s: B=%d h=%d w=%d: need 3*B*h*w < 2^31", what, B, h, w);
+  REQUIRE(in_dtype == AUG_U8 || (aligned(image1, 4) && aligned(image2, 4)), AUG_ERR_BAD_ARG, "%s: fp32 inputs must be 4-byte aligned", what);
+  REQUIRE(out_dtype == AUG_U8 || (aligned(out1, 4) && aligned(out2, 4)), AUG_ERR_BAD_ARG, "%s: fp32 outputs must be 4-byte aligned", what);
+  REQUIRE(aligned(workspace, 8), AUG_ERR_BAD_ARG, "%s: the workspace must be 8-byte aligned", what);
   for (int b = 0; b < B; ++b) {  // all samples before the first launch
     const aug_sample& S = samples[b];
     for (int img = 0; img < 2; ++img)
       if (int rc = check_image_params(b, img, S.img[img])) return rc;
-    AUG_REQUIRE(S.shared == 0 || S.shared == 1, AUG_ERR_BAD_ARG, "%s: sample %d: shared = %d, 0 or 1 expected", what, b, S.shared);
-    AUG_REQUIRE(S.n_rects >= 0 && S.n_rects <= AUG_MAX_RECTS, AUG_ERR_BAD_ARG, "%s: sample %d: %d rectangles, 0..%d expected", what, b, S.n_rects,
-                AUG_MAX_RECTS);
+    REQUIRE(S.shared == 0 || S.shared == 1, AUG_ERR_BAD_ARG, "%s: sample %d: shared = %d, 0 or 1 expected", what, b, S.shared);
+    REQUIRE(S.n_rects >= 0 && S.n_rects <= AUG_MAX_RECTS, AUG_ERR_BAD_ARG, "%s: sample %d: %d rectangles, 0..%d expected", what, b, S.n_rects,
+            AUG_MAX_RECTS);
     for (int r = 0; r < S.n_rects; ++r) {
       const int* q = S.rect[r];
-      AUG_REQUIRE(q[2] > 0 && q[3] > 0, AUG_ERR_BAD_ARG, "%s: sample %d rectangle %d: extent %d x %d must be positive", what, b, r, q[2], q[3]);
-      AUG_REQUIRE(q[0] >= 0 && q[0] < w && q[1] >= 0 && q[1] < h, AUG_ERR_BAD_ARG, "%s: sample %d rectangle %d: origin (%d, %d) outside the %d x %d frame",
-                  what, b, r, q[0], q[1], h, w);
+      REQUIRE(q[2] > 0 && q[3] > 0, AUG_ERR_BAD_ARG, "%s: sample %d rectangle %d: extent %d x %d must be positive", what, b, r, q[2], q[3]);
+      REQUIRE(q[0] >= 0 && q[0] < w && q[1] >= 0 && q[1] < h, AUG_ERR_BAD_ARG, "%s: sample %d rectangle %d: origin (%d, %d) outside the %d x %d frame",
+              what, b, r, q[0], q[1], h, w);
     }
   }
   const int64_t need = aug_workspace_bytes(B, h, w);
-  AUG_REQUIRE(workspace_bytes >= need, AUG_ERR_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", what, (long long)workspace_bytes, (long long)need);
+  REQUIRE(workspace_bytes >= need, AUG_ERR_WORKSPACE, "%s: workspace of %lld bytes, %lld needed", what, (long long)workspace_bytes, (long long)need);
   const int64_t elems = 3ll * B * h * w;
   const int64_t nin = elems * (in_dtype == AUG_F32 ? 4 : 1), nout = elems * (out_dtype == AUG_F32 ? 4 : 1);
   const void* outs[2] = {out1, out2};
   for (int o = 0; o < 2; ++o) {
-    AUG_REQUIRE(!overlap(outs[o], nout, image1, nin) && !overlap(outs[o], nout, image2, nin), AUG_ERR_ALIAS, "%s: out%d overlaps an input", what, o + 1);
-    AUG_REQUIRE(!overlap(outs[o], nout, workspace, need), AUG_ERR_ALIAS, "%s: out%d overlaps the workspace", what, o + 1);
-    AUG_REQUIRE(gamma_lut == nullptr || !overlap(outs[o], nout, gamma_lut, (int64_t)B * 512), AUG_ERR_ALIAS, "%s: out%d overlaps gamma_lut", what, o + 1);
+    REQUIRE(!overlap(outs[o], nout, image1, nin) && !overlap(outs[o], nout, image2, nin), AUG_ERR_ALIAS, "%s: out%d overlaps an input", what, o + 1);
+    REQUIRE(!overlap(outs[o], nout, workspace, need), AUG_ERR_ALIAS, "%s: out%d overlaps the workspace", what, o + 1);
+    REQUIRE(gamma_lut == nullptr || !overlap(outs[o], nout, gamma_lut, (int64_t)B * 512), AUG_ERR_ALIAS, "%s: out%d overlaps gamma_lut", what, o + 1);
   }
-  AUG_REQUIRE(!overlap(out1, nout, out2, nout), AUG_ERR_ALIAS, "%s: out1 overlaps out2", what);
-  AUG_REQUIRE(!overlap(workspace, need, image1, nin) && !overlap(workspace, need, image2, nin), AUG_ERR_ALIAS, "%s: the workspace overlaps an input", what);
+  REQUIRE(!overlap(out1, nout, out2, nout), AUG_ERR_ALIAS, "%s: out1 overlaps out2", what);
+  REQUIRE(!overlap(workspace, need, image1, nin) && !overlap(workspace, need, image2, nin), AUG_ERR_ALIAS, "%s: the workspace overlaps an input", what);
 
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   u64* ws = reinterpret_cast<u64*>(workspace);

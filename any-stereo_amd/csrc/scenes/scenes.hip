@@ -16,11 +16,11 @@
 // copy of the derivation is checked against it without a GPU.
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../../include/anystereo_scenes.h"
+#include "../host/errstate.h"
 
 #pragma clang fp contract(off)
 
@@ -32,24 +32,6 @@ constexpr float kInv24 = 5.9604644775390625e-08f;  // 2^-24
 constexpr int kSlotKind = 0, kSlotCu = 1, kSlotCv = 2, kSlotA = 3, kSlotB = 4, kSlotK = 5, kSlotAlpha = 6, kSlotBeta = 7, kSlotGamma = 8,
               kSlotColour = 9, kSlotOctave = 32;
 constexpr int kSlotNoise = SCN_MAX_LAYERS * 64;  // the per-value noise of image2
-
-char* err_buf() {
-  static thread_local char buf[512] = "ok";
-  return buf;
-}
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(err_buf(), 512, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define SCN_REQUIRE(cond, code, ...)               \
-  do {                                             \
-    if (!(cond)) return fail(code, __VA_ARGS__);   \
-  } while (0)
 
 struct Layer {
   int kind;
@@ -318,26 +300,20 @@ __global__ __launch_bounds__(kThreads) void at_kernel(AtTable tab, scn_spec sp, 
 
 // ---- host side ----
 int check_spec(const char* what, const scn_spec* sp) {
-  SCN_REQUIRE(sp != nullptr, SCN_ERR_BAD_ARG, "%s: null spec", what);
-  SCN_REQUIRE(sp->n_layers >= 1 && sp->n_layers <= SCN_MAX_LAYERS, SCN_ERR_BAD_ARG, "%s: n_layers=%d outside [1, %d]", what, sp->n_layers,
-              SCN_MAX_LAYERS);
-  SCN_REQUIRE(sp->octaves >= 1 && sp->octaves <= SCN_MAX_OCTAVES, SCN_ERR_BAD_ARG, "%s: octaves=%d outside [1, %d]", what, sp->octaves,
-              SCN_MAX_OCTAVES);
-  SCN_REQUIRE(sp->aspect > 0.f && sp->size_min > 0.f && sp->size_max >= sp->size_min && sp->lattice > 0.f, SCN_ERR_BAD_ARG,
-              "%s: aspect=%g, size_min=%g, size_max=%g, lattice=%g: positive values and size_min <= size_max expected", what,
-              (double)sp->aspect, (double)sp->size_min, (double)sp->size_max, (double)sp->lattice);
-  SCN_REQUIRE(fabsf(sp->slope_max) < 1.f && fabsf(sp->bg_slope) < 1.f, SCN_ERR_BAD_ARG,
-              "%s: slope_max=%g, bg_slope=%g: a plane with |beta| >= 1 has no right view", what, (double)sp->slope_max, (double)sp->bg_slope);
+  REQUIRE(sp != nullptr, SCN_ERR_BAD_ARG, "%s: null spec", what);
+  REQUIRE(sp->n_layers >= 1 && sp->n_layers <= SCN_MAX_LAYERS, SCN_ERR_BAD_ARG, "%s: n_layers=%d outside [1, %d]", what, sp->n_layers,
+          SCN_MAX_LAYERS);
+  REQUIRE(sp->octaves >= 1 && sp->octaves <= SCN_MAX_OCTAVES, SCN_ERR_BAD_ARG, "%s: octaves=%d outside [1, %d]", what, sp->octaves,
+          SCN_MAX_OCTAVES);
+  REQUIRE(sp->aspect > 0.f && sp->size_min > 0.f && sp->size_max >= sp->size_min && sp->lattice > 0.f, SCN_ERR_BAD_ARG,
+          "%s: aspect=%g, size_min=%g, size_max=%g, lattice=%g: positive values and size_min <= size_max expected", what,
+          (double)sp->aspect, (double)sp->size_min, (double)sp->size_max, (double)sp->lattice);
+  REQUIRE(fabsf(sp->slope_max) < 1.f && fabsf(sp->bg_slope) < 1.f, SCN_ERR_BAD_ARG,
+          "%s: slope_max=%g, bg_slope=%g: a plane with |beta| >= 1 has no right view", what, (double)sp->slope_max, (double)sp->bg_slope);
   return SCN_OK;
 }
 
 inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(SCN_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-  return SCN_OK;
-}
 
 inline unsigned cdiv(int64_t a, int64_t b) { return (unsigned)((a + b - 1) / b); }
 
@@ -351,7 +327,7 @@ const char* scn_last_error_string(void) { return err_buf(); }
 
 int scn_layers(const scn_spec* spec, uint64_t seed, int index, float* out) {
   if (int rc = check_spec("scn_layers", spec)) return rc;
-  SCN_REQUIRE(out != nullptr, SCN_ERR_BAD_ARG, "scn_layers: null output");
+  REQUIRE(out != nullptr, SCN_ERR_BAD_ARG, "scn_layers: null output");
   const uint32_t base = scene_key(seed, index);
   for (int l = 0; l < spec->n_layers; ++l) {
     Layer L;
@@ -366,27 +342,27 @@ int scn_layers(const scn_spec* spec, uint64_t seed, int index, float* out) {
 
 int scn_render_pair(float* image1, float* image2, int B, int h, int w, const scn_spec* spec, uint64_t seed, int index0, void* stream) {
   if (int rc = check_spec("scn_render_pair", spec)) return rc;
-  SCN_REQUIRE(image1 != nullptr && image2 != nullptr, SCN_ERR_BAD_ARG, "scn_render_pair: null image");
-  SCN_REQUIRE(aligned(image1, 4) && aligned(image2, 4), SCN_ERR_BAD_ARG, "scn_render_pair: images must be 4-byte aligned");
-  SCN_REQUIRE(B >= 1 && h >= 1 && w >= 1, SCN_ERR_BAD_ARG, "scn_render_pair: B=%d h=%d w=%d must be positive", B, h, w);
-  SCN_REQUIRE(B <= 65535 && 3ll * B * h * w < (1ll << 31), SCN_ERR_BAD_SHAPE, "scn_render_pair: B=%d h=%d w=%d: need B <= 65535 and 3*B*h*w < 2^31",
-              B, h, w);
+  REQUIRE(image1 != nullptr && image2 != nullptr, SCN_ERR_BAD_ARG, "scn_render_pair: null image");
+  REQUIRE(aligned(image1, 4) && aligned(image2, 4), SCN_ERR_BAD_ARG, "scn_render_pair: images must be 4-byte aligned");
+  REQUIRE(B >= 1 && h >= 1 && w >= 1, SCN_ERR_BAD_ARG, "scn_render_pair: B=%d h=%d w=%d must be positive", B, h, w);
+  REQUIRE(B <= 65535 && 3ll * B * h * w < (1ll << 31), SCN_ERR_BAD_SHAPE, "scn_render_pair: B=%d h=%d w=%d: need B <= 65535 and 3*B*h*w < 2^31",
+          B, h, w);
   hipLaunchKernelGGL(render_kernel, dim3(cdiv((int64_t)h * w, kThreads), (unsigned)B), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream),
                      *spec, seed, index0, image1, image2, h, w, axis(h), axis(w));
-  return check_launch("scn_render_pair");
+  return check_launch("scn_render_pair", SCN_ERR_LAUNCH);
 }
 
 int scn_ground_truth(const scn_gt_sample* table, int n, const scn_spec* spec, uint64_t seed, void* stream) {
   if (int rc = check_spec("scn_ground_truth", spec)) return rc;
-  SCN_REQUIRE(table != nullptr, SCN_ERR_BAD_ARG, "scn_ground_truth: null table");
-  SCN_REQUIRE(n >= 1, SCN_ERR_BAD_ARG, "scn_ground_truth: n=%d samples", n);
+  REQUIRE(table != nullptr, SCN_ERR_BAD_ARG, "scn_ground_truth: null table");
+  REQUIRE(n >= 1, SCN_ERR_BAD_ARG, "scn_ground_truth: n=%d samples", n);
   for (int i = 0; i < n; ++i) {  // all samples before the first launch
     const scn_gt_sample& s = table[i];
-    SCN_REQUIRE(s.h >= 1 && s.w >= 1, SCN_ERR_BAD_ARG, "scn_ground_truth: sample %d: h=%d w=%d must be positive", i, s.h, s.w);
-    SCN_REQUIRE((int64_t)s.h * s.w < (1ll << 31), SCN_ERR_BAD_SHAPE, "scn_ground_truth: sample %d: h*w = %lld >= 2^31", i,
-                (long long)s.h * s.w);
-    SCN_REQUIRE(s.disp != nullptr || s.disp_right != nullptr || s.noc != nullptr, SCN_ERR_BAD_ARG, "scn_ground_truth: sample %d: no output", i);
-    SCN_REQUIRE(aligned(s.disp, 4) && aligned(s.disp_right, 4), SCN_ERR_BAD_ARG, "scn_ground_truth: sample %d: outputs must be 4-byte aligned", i);
+    REQUIRE(s.h >= 1 && s.w >= 1, SCN_ERR_BAD_ARG, "scn_ground_truth: sample %d: h=%d w=%d must be positive", i, s.h, s.w);
+    REQUIRE((int64_t)s.h * s.w < (1ll << 31), SCN_ERR_BAD_SHAPE, "scn_ground_truth: sample %d: h*w = %lld >= 2^31", i,
+            (long long)s.h * s.w);
+    REQUIRE(s.disp != nullptr || s.disp_right != nullptr || s.noc != nullptr, SCN_ERR_BAD_ARG, "scn_ground_truth: sample %d: no output", i);
+    REQUIRE(aligned(s.disp, 4) && aligned(s.disp_right, 4), SCN_ERR_BAD_ARG, "scn_ground_truth: sample %d: outputs must be 4-byte aligned", i);
   }
   for (int i0 = 0; i0 < n; i0 += SCN_MAX_BATCH) {
     const int nb = n - i0 < SCN_MAX_BATCH ? n - i0 : SCN_MAX_BATCH;
@@ -399,7 +375,7 @@ int scn_ground_truth(const scn_gt_sample* table, int n, const scn_spec* spec, ui
     }
     hipLaunchKernelGGL(gt_kernel, dim3(cdiv(most, kThreads), (unsigned)nb), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), t, *spec,
                        seed);
-    if (int rc = check_launch("scn_ground_truth")) return rc;
+    if (int rc = check_launch("scn_ground_truth", SCN_ERR_LAUNCH)) return rc;
   }
   return SCN_OK;
 }
@@ -407,11 +383,11 @@ int scn_ground_truth(const scn_gt_sample* table, int n, const scn_spec* spec, ui
 int scn_disparity_at(const float* coord, float* out, unsigned char* noc, int B, int Q, const float* mul, const int* index, int right_view,
                      const scn_spec* spec, uint64_t seed, void* stream) {
   if (int rc = check_spec("scn_disparity_at", spec)) return rc;
-  SCN_REQUIRE(coord != nullptr && out != nullptr && mul != nullptr && index != nullptr, SCN_ERR_BAD_ARG, "scn_disparity_at: null pointer");
-  SCN_REQUIRE(aligned(coord, 8) && aligned(out, 4), SCN_ERR_BAD_ARG, "scn_disparity_at: coord must be 8-byte and out 4-byte aligned");
-  SCN_REQUIRE(B >= 1 && Q >= 1, SCN_ERR_BAD_ARG, "scn_disparity_at: B=%d Q=%d must be positive", B, Q);
-  SCN_REQUIRE(2ll * B * Q < (1ll << 31), SCN_ERR_BAD_SHAPE, "scn_disparity_at: B=%d Q=%d: need 2*B*Q < 2^31", B, Q);
-  SCN_REQUIRE(!(right_view && noc != nullptr), SCN_ERR_BAD_ARG, "scn_disparity_at: noc is defined for the left view only");
+  REQUIRE(coord != nullptr && out != nullptr && mul != nullptr && index != nullptr, SCN_ERR_BAD_ARG, "scn_disparity_at: null pointer");
+  REQUIRE(aligned(coord, 8) && aligned(out, 4), SCN_ERR_BAD_ARG, "scn_disparity_at: coord must be 8-byte and out 4-byte aligned");
+  REQUIRE(B >= 1 && Q >= 1, SCN_ERR_BAD_ARG, "scn_disparity_at: B=%d Q=%d must be positive", B, Q);
+  REQUIRE(2ll * B * Q < (1ll << 31), SCN_ERR_BAD_SHAPE, "scn_disparity_at: B=%d Q=%d: need 2*B*Q < 2^31", B, Q);
+  REQUIRE(!(right_view && noc != nullptr), SCN_ERR_BAD_ARG, "scn_disparity_at: noc is defined for the left view only");
   for (int b0 = 0; b0 < B; b0 += SCN_MAX_BATCH) {
     const int nb = B - b0 < SCN_MAX_BATCH ? B - b0 : SCN_MAX_BATCH;
     AtTable t;
@@ -422,7 +398,7 @@ int scn_disparity_at(const float* coord, float* out, unsigned char* noc, int B, 
     const int64_t off = (int64_t)b0 * Q;
     hipLaunchKernelGGL(at_kernel, dim3(cdiv(Q, kThreads), (unsigned)nb), dim3(kThreads), 0, reinterpret_cast<hipStream_t>(stream), t, *spec, seed,
                        reinterpret_cast<const float2*>(coord) + off, out + off, noc == nullptr ? nullptr : noc + off, Q, right_view ? 1 : 0);
-    if (int rc = check_launch("scn_disparity_at")) return rc;
+    if (int rc = check_launch("scn_disparity_at", SCN_ERR_LAUNCH)) return rc;
   }
   return SCN_OK;
 }

@@ -13,12 +13,12 @@
 // FMA contraction is off for the whole file (cubic.h switches it off at file scope; stated again below for the reader).
 #include <hip/hip_runtime.h>
 #include <math.h>
-#include <stdarg.h>
 #include <stdint.h>
 #include <stdio.h>
 
 #include "../../../include/anystereo_spatial.h"
 #include "../cubic.h"
+#include "../host/errstate.h"
 
 #pragma clang fp contract(off)
 
@@ -26,24 +26,6 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxBlocksX = 1024;  // truth_kernel walks its crop with a grid stride
-
-char* err_buf() {
-  static thread_local char buf[512] = "ok";
-  return buf;
-}
-
-int fail(int code, const char* fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(err_buf(), 512, fmt, ap);
-  va_end(ap);
-  return code;
-}
-
-#define SPT_REQUIRE(cond, code, ...)             \
-  do {                                           \
-    if (!(cond)) return fail(code, __VA_ARGS__); \
-  } while (0)
 
 // what a kernel knows of one sample
 struct Dev {
@@ -218,12 +200,6 @@ __global__ __launch_bounds__(kThreads) void truth_kernel(Table tab, const float*
 }
 
 // ---- the host side ----
-int check_launch(const char* what) {
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(SPT_ERR_LAUNCH, "%s: %s", what, hipGetErrorString(e));
-  return SPT_OK;
-}
-
 inline bool aligned(const void* p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
 inline bool overlap(const void* a, int64_t na, const void* b, int64_t nb) {
@@ -239,43 +215,43 @@ inline int64_t elements(int B, int h, int w) {
 }
 
 int frame_size(const char* what, int H, int W, int rescale, double sx, double sy, int* fh, int* fw) {
-  SPT_REQUIRE(H >= 1 && W >= 1, SPT_ERR_BAD_ARG, "%s: H=%d W=%d must be positive", what, H, W);
-  SPT_REQUIRE(rescale == 0 || rescale == 1, SPT_ERR_BAD_ARG, "%s: rescale = %d, 0 or 1 expected", what, rescale);
+  REQUIRE(H >= 1 && W >= 1, SPT_ERR_BAD_ARG, "%s: H=%d W=%d must be positive", what, H, W);
+  REQUIRE(rescale == 0 || rescale == 1, SPT_ERR_BAD_ARG, "%s: rescale = %d, 0 or 1 expected", what, rescale);
   if (!rescale) {
     *fh = H;
     *fw = W;
     return SPT_OK;
   }
-  SPT_REQUIRE(isfinite(sx) && isfinite(sy) && sx >= SPT_MIN_SCALE && sx <= SPT_MAX_SCALE && sy >= SPT_MIN_SCALE && sy <= SPT_MAX_SCALE, SPT_ERR_BAD_ARG,
-              "%s: scale_x = %g, scale_y = %g outside [%g, %g]", what, sx, sy, SPT_MIN_SCALE, SPT_MAX_SCALE);
+  REQUIRE(isfinite(sx) && isfinite(sy) && sx >= SPT_MIN_SCALE && sx <= SPT_MAX_SCALE && sy >= SPT_MIN_SCALE && sy <= SPT_MAX_SCALE, SPT_ERR_BAD_ARG,
+          "%s: scale_x = %g, scale_y = %g outside [%g, %g]", what, sx, sy, SPT_MIN_SCALE, SPT_MAX_SCALE);
   const double h = rint((double)H * sy), w = rint((double)W * sx);  // half to even: the default rounding mode
-  SPT_REQUIRE(h >= 1.0 && w >= 1.0, SPT_ERR_BAD_ARG, "%s: an empty rescaled frame %g x %g", what, h, w);
-  SPT_REQUIRE(h * w < 2147483648.0, SPT_ERR_BAD_SHAPE, "%s: a rescaled frame of %g x %g pixels", what, h, w);
+  REQUIRE(h >= 1.0 && w >= 1.0, SPT_ERR_BAD_ARG, "%s: an empty rescaled frame %g x %g", what, h, w);
+  REQUIRE(h * w < 2147483648.0, SPT_ERR_BAD_SHAPE, "%s: a rescaled frame of %g x %g pixels", what, h, w);
   *fh = (int)h;
   *fw = (int)w;
   return SPT_OK;
 }
 
 int validate(const char* what, const spt_sample* samples, int B, int H, int W, int out_h, int out_w) {
-  SPT_REQUIRE(samples != nullptr, SPT_ERR_BAD_ARG, "%s: null pointer", what);
-  SPT_REQUIRE(B >= 1 && H >= 1 && W >= 1, SPT_ERR_BAD_ARG, "%s: B=%d H=%d W=%d must be positive", what, B, H, W);
-  SPT_REQUIRE((out_h == 0 && out_w == 0) || (out_h >= 1 && out_w >= 1), SPT_ERR_BAD_ARG, "%s: out size %d x %d: both 0 or both positive", what, out_h, out_w);
-  SPT_REQUIRE(elements(B, H, W) < (1ll << 31), SPT_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d: need 3*B*H*W < 2^31", what, B, H, W);
+  REQUIRE(samples != nullptr, SPT_ERR_BAD_ARG, "%s: null pointer", what);
+  REQUIRE(B >= 1 && H >= 1 && W >= 1, SPT_ERR_BAD_ARG, "%s: B=%d H=%d W=%d must be positive", what, B, H, W);
+  REQUIRE((out_h == 0 && out_w == 0) || (out_h >= 1 && out_w >= 1), SPT_ERR_BAD_ARG, "%s: out size %d x %d: both 0 or both positive", what, out_h, out_w);
+  REQUIRE(elements(B, H, W) < (1ll << 31), SPT_ERR_BAD_SHAPE, "%s: B=%d H=%d W=%d: need 3*B*H*W < 2^31", what, B, H, W);
   for (int b = 0; b < B; ++b) {
     const spt_sample& P = samples[b];
     int fh, fw;
     if (int rc = frame_size(what, H, W, P.rescale, P.scale_x, P.scale_y, &fh, &fw)) return rc;
-    SPT_REQUIRE(P.flip >= SPT_FLIP_NONE && P.flip <= SPT_FLIP_V, SPT_ERR_BAD_ARG, "%s: sample %d: flip = %d", what, b, P.flip);
-    SPT_REQUIRE(P.ch >= 1 && P.cw >= 1, SPT_ERR_BAD_ARG, "%s: sample %d: crop %d x %d must be positive", what, b, P.ch, P.cw);
-    SPT_REQUIRE(P.y0 >= 0 && P.x0 >= 0 && (int64_t)P.y0 + P.ch <= fh && (int64_t)P.x0 + P.cw <= fw, SPT_ERR_CROP,
-                "%s: sample %d: the crop %d x %d at (%d, %d) leaves the %d x %d frame", what, b, P.ch, P.cw, P.y0, P.x0, fh, fw);
-    SPT_REQUIRE((int64_t)P.y0 + P.dy2 >= 0 && (int64_t)P.y0 + P.dy2 + P.ch <= fh, SPT_ERR_CROP,
-                "%s: sample %d: image2's crop at y0 + dy2 = %d + %d leaves the %d x %d frame", what, b, P.y0, P.dy2, fh, fw);
-    SPT_REQUIRE(out_h != 0 || (P.ch == samples[0].ch && P.cw == samples[0].cw), SPT_ERR_CROP,
-                "%s: sample %d: crop %d x %d differs from sample 0's %d x %d and there is no out size", what, b, P.ch, P.cw, samples[0].ch, samples[0].cw);
+    REQUIRE(P.flip >= SPT_FLIP_NONE && P.flip <= SPT_FLIP_V, SPT_ERR_BAD_ARG, "%s: sample %d: flip = %d", what, b, P.flip);
+    REQUIRE(P.ch >= 1 && P.cw >= 1, SPT_ERR_BAD_ARG, "%s: sample %d: crop %d x %d must be positive", what, b, P.ch, P.cw);
+    REQUIRE(P.y0 >= 0 && P.x0 >= 0 && (int64_t)P.y0 + P.ch <= fh && (int64_t)P.x0 + P.cw <= fw, SPT_ERR_CROP,
+            "%s: sample %d: the crop %d x %d at (%d, %d) leaves the %d x %d frame", what, b, P.ch, P.cw, P.y0, P.x0, fh, fw);
+    REQUIRE((int64_t)P.y0 + P.dy2 >= 0 && (int64_t)P.y0 + P.dy2 + P.ch <= fh, SPT_ERR_CROP,
+            "%s: sample %d: image2's crop at y0 + dy2 = %d + %d leaves the %d x %d frame", what, b, P.y0, P.dy2, fh, fw);
+    REQUIRE(out_h != 0 || (P.ch == samples[0].ch && P.cw == samples[0].cw), SPT_ERR_CROP,
+            "%s: sample %d: crop %d x %d differs from sample 0's %d x %d and there is no out size", what, b, P.ch, P.cw, samples[0].ch, samples[0].cw);
   }
   const int h_out = out_h ? out_h : samples[0].ch, w_out = out_w ? out_w : samples[0].cw;
-  SPT_REQUIRE(elements(B, h_out, w_out) < (1ll << 31), SPT_ERR_BAD_SHAPE, "%s: B=%d out %d x %d: need 3*B*h*w < 2^31", what, B, h_out, w_out);
+  REQUIRE(elements(B, h_out, w_out) < (1ll << 31), SPT_ERR_BAD_SHAPE, "%s: B=%d out %d x %d: need 3*B*h*w < 2^31", what, B, h_out, w_out);
   return SPT_OK;
 }
 
@@ -313,7 +289,7 @@ int launch_chunks(const TIn* in1, const TIn* in2, const float* disp, const unsig
       hipLaunchKernelGGL((image_kernel<TIn, TOut, true>), grid, dim3(kThreads), 0, stream, t, i1, i2, o1, o2, H, W, h_out, w_out);
     else
       hipLaunchKernelGGL((image_kernel<TIn, TOut, false>), grid, dim3(kThreads), 0, stream, t, i1, i2, o1, o2, H, W, h_out, w_out);
-    if (int rc = check_launch("spt_spatial_pair (images)")) return rc;
+    if (int rc = check_launch("spt_spatial_pair (images)", SPT_ERR_LAUNCH)) return rc;
     int64_t gx = (most + kThreads - 1) / kThreads;
     if (gx > kMaxBlocksX) gx = kMaxBlocksX;
     const dim3 tgrid((unsigned)gx, 1u, (unsigned)nb);
@@ -322,7 +298,7 @@ int launch_chunks(const TIn* in1, const TIn* in2, const float* disp, const unsig
       hipLaunchKernelGGL((truth_kernel<true>), tgrid, dim3(kThreads), 0, stream, t, d, valid + (int64_t)b0 * plane_in, H, W);
     else
       hipLaunchKernelGGL((truth_kernel<false>), tgrid, dim3(kThreads), 0, stream, t, d, (const unsigned char*)nullptr, H, W);
-    if (int rc = check_launch("spt_spatial_pair (ground truth)")) return rc;
+    if (int rc = check_launch("spt_spatial_pair (ground truth)", SPT_ERR_LAUNCH)) return rc;
   }
   return SPT_OK;
 }
@@ -336,7 +312,7 @@ int spt_abi_version(void) { return 1; }
 const char* spt_last_error_string(void) { return err_buf(); }
 
 int spt_frame_size(int H, int W, int rescale, double scale_x, double scale_y, int* fh, int* fw) {
-  SPT_REQUIRE(fh != nullptr && fw != nullptr, SPT_ERR_BAD_ARG, "spt_frame_size: null pointer");
+  REQUIRE(fh != nullptr && fw != nullptr, SPT_ERR_BAD_ARG, "spt_frame_size: null pointer");
   return frame_size("spt_frame_size", H, W, rescale, scale_x, scale_y, fh, fw);
 }
 
@@ -346,18 +322,18 @@ int spt_spatial_pair(const void* image1, const void* image2, int in_dtype, const
                      const spt_sample* samples, void* out1, void* out2, int out_dtype, int out_h, int out_w, float* const* disp_out,
                      unsigned char* const* valid_out, void* stream) {
   const char* what = "spt_spatial_pair";
-  SPT_REQUIRE(image1 != nullptr && image2 != nullptr && disp != nullptr && samples != nullptr && out1 != nullptr && out2 != nullptr && disp_out != nullptr,
-              SPT_ERR_BAD_ARG, "%s: null pointer", what);
-  SPT_REQUIRE((valid == nullptr) == (valid_out == nullptr), SPT_ERR_BAD_ARG, "%s: valid and valid_out go together (the sparse form) or are both NULL", what);
-  SPT_REQUIRE((in_dtype == SPT_U8 || in_dtype == SPT_F32) && (out_dtype == SPT_U8 || out_dtype == SPT_F32), SPT_ERR_BAD_ARG,
-              "%s: in_dtype=%d out_dtype=%d: SPT_U8 or SPT_F32 expected", what, in_dtype, out_dtype);
+  REQUIRE(image1 != nullptr && image2 != nullptr && disp != nullptr && samples != nullptr && out1 != nullptr && out2 != nullptr && disp_out != nullptr,
+          SPT_ERR_BAD_ARG, "%s: null pointer", what);
+  REQUIRE((valid == nullptr) == (valid_out == nullptr), SPT_ERR_BAD_ARG, "%s: valid and valid_out go together (the sparse form) or are both NULL", what);
+  REQUIRE((in_dtype == SPT_U8 || in_dtype == SPT_F32) && (out_dtype == SPT_U8 || out_dtype == SPT_F32), SPT_ERR_BAD_ARG,
+          "%s: in_dtype=%d out_dtype=%d: SPT_U8 or SPT_F32 expected", what, in_dtype, out_dtype);
   if (int rc = validate(what, samples, B, H, W, out_h, out_w)) return rc;
-  SPT_REQUIRE(in_dtype == SPT_U8 || (aligned(image1, 4) && aligned(image2, 4)), SPT_ERR_BAD_ARG, "%s: fp32 inputs must be 4-byte aligned", what);
-  SPT_REQUIRE(out_dtype == SPT_U8 || (aligned(out1, 4) && aligned(out2, 4)), SPT_ERR_BAD_ARG, "%s: fp32 outputs must be 4-byte aligned", what);
-  SPT_REQUIRE(aligned(disp, 4), SPT_ERR_BAD_ARG, "%s: disp must be 4-byte aligned", what);
+  REQUIRE(in_dtype == SPT_U8 || (aligned(image1, 4) && aligned(image2, 4)), SPT_ERR_BAD_ARG, "%s: fp32 inputs must be 4-byte aligned", what);
+  REQUIRE(out_dtype == SPT_U8 || (aligned(out1, 4) && aligned(out2, 4)), SPT_ERR_BAD_ARG, "%s: fp32 outputs must be 4-byte aligned", what);
+  REQUIRE(aligned(disp, 4), SPT_ERR_BAD_ARG, "%s: disp must be 4-byte aligned", what);
   for (int b = 0; b < B; ++b) {
-    SPT_REQUIRE(disp_out[b] != nullptr && aligned(disp_out[b], 4), SPT_ERR_BAD_ARG, "%s: disp_out[%d] is NULL or not 4-byte aligned", what, b);
-    SPT_REQUIRE(valid_out == nullptr || valid_out[b] != nullptr, SPT_ERR_BAD_ARG, "%s: valid_out[%d] is NULL", what, b);
+    REQUIRE(disp_out[b] != nullptr && aligned(disp_out[b], 4), SPT_ERR_BAD_ARG, "%s: disp_out[%d] is NULL or not 4-byte aligned", what, b);
+    REQUIRE(valid_out == nullptr || valid_out[b] != nullptr, SPT_ERR_BAD_ARG, "%s: valid_out[%d] is NULL", what, b);
   }
   // aliasing: every output against every input and every other output
   const int h_out = out_h ? out_h : samples[0].ch, w_out = out_w ? out_w : samples[0].cw;
@@ -383,12 +359,12 @@ int spt_spatial_pair(const void* image1, const void* image2, int in_dtype, const
     int64_t n;
     out_at(o, &p, &n);
     for (int i = 0; i < 4; ++i)
-      SPT_REQUIRE(nins[i] == 0 || !overlap(p, n, ins[i], nins[i]), SPT_ERR_ALIAS, "%s: output %d overlaps input %d", what, o, i);
+      REQUIRE(nins[i] == 0 || !overlap(p, n, ins[i], nins[i]), SPT_ERR_ALIAS, "%s: output %d overlaps input %d", what, o, i);
     for (int o2 = 0; o2 < o; ++o2) {
       const void* p2;
       int64_t n2;
       out_at(o2, &p2, &n2);
-      SPT_REQUIRE(!overlap(p, n, p2, n2), SPT_ERR_ALIAS, "%s: output %d overlaps output %d", what, o, o2);
+      REQUIRE(!overlap(p, n, p2, n2), SPT_ERR_ALIAS, "%s: output %d overlaps output %d", what, o, o2);
     }
   }
 

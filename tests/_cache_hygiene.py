@@ -1,5 +1,5 @@
-"""What a GPU test module that fills device memory with random bytes does when it is done.  A helper module (like tests/_guarded.py),
-not a test file; tests/test_augment_gpu.py carries an earlier copy of the same function of its own."""
+"""What a GPU test module that fills device memory with random bytes does when it is done (tests/test_augment_gpu.py,
+tests/test_spatial_gpu.py).  A helper module (like tests/_guarded.py), not a test file."""
 import gc
 
 import torch

@@ -21,6 +21,7 @@ This is a helper module (like tests/_conv_cases.py), not a plugin: nothing is pa
 """
 from __future__ import annotations
 
+import contextlib
 import operator
 import os
 import sys
@@ -269,6 +270,31 @@ class _ZeroFill(guarded):
 
 
 _ZERO = _ZeroFill(0)
+
+
+# ---- counting the calls made under a guard ------------------------------------------------------------------------------------
+
+@contextlib.contextmanager
+def counted(L, calls: dict):
+    """For the duration of the block every function of `L.SIGNATURES` on the loaded library `L.load()` (a binding module:
+    anystereo._lib, _scenes_lib, ...) counts into `calls[name]` the calls made while a guarded context is active; the functions
+    themselves are put back on exit.  A module's "every launching symbol was called under a guard" test reads `calls`."""
+    lib = L.load()
+    orig = {n: getattr(lib, n) for n in L.SIGNATURES}
+
+    def wrap(name, fn):
+        def call(*a):
+            if _ACTIVE:
+                calls[name] = calls.get(name, 0) + 1
+            return fn(*a)
+        return call
+    for n, fn in orig.items():
+        setattr(lib, n, wrap(n, fn))
+    try:
+        yield
+    finally:
+        for n, fn in orig.items():
+            setattr(lib, n, fn)
 
 
 # ---- the three-run comparison -------------------------------------------------------------------------------------------------

@@ -12,6 +12,7 @@ import pytest
 import torch
 
 import _augment_cases as K
+from _headers import declared_symbols
 from anystereo.harness import augment as A
 
 
@@ -196,7 +197,7 @@ def test_library_loads_and_binds_every_symbol_of_the_header():
     info = L.library_info()
     assert info["matches_sources"] is True and info["abi"] == 1
     header = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "include", "anystereo_augment.h")).read()
-    declared = set(re.findall(r"\b(aug_[a-z_]+)\s*\(", header))
+    declared = declared_symbols("augment")
     assert declared == set(L.SIGNATURES), declared ^ set(L.SIGNATURES)
     assert set(L.LAUNCHING) == {"aug_photometric_pair"}
     for h, w in ((3, 5), (160, 320), (540, 960), (4096, 4096)):

@@ -10,6 +10,7 @@ import torch
 
 import _augment_cases as K
 import _guarded as GD
+from _cache_hygiene import hand_the_cache_back_zeroed
 from anystereo.harness import augment as A
 
 pytestmark = pytest.mark.gpu
@@ -21,46 +22,11 @@ CALLS = {}  # aug_* symbol -> calls made while a guarded context was active
 @pytest.fixture(scope="module", autouse=True)
 def _counted_library():
     from anystereo import _augment_lib as L
-    lib = L.load()
-    orig = {n: getattr(lib, n) for n in L.SIGNATURES}
-
-    def wrap(name, fn):
-        def call(*a):
-            if GD._ACTIVE:
-                CALLS[name] = CALLS.get(name, 0) + 1
-            return fn(*a)
-        return call
-    for n, fn in orig.items():
-        setattr(lib, n, wrap(n, fn))
     try:
-        yield
+        with GD.counted(L, CALLS):
+            yield
     finally:
-        for n, fn in orig.items():
-            setattr(lib, n, fn)
-        _hand_the_cache_back_zeroed()
-
-
-def _hand_the_cache_back_zeroed():
-    """Leave the caching allocator as the rest of the suite has always found it (tests/_guarded.py zero-fills its buffers for the
-    same reason): this module's freed blocks hold random image bytes and partial sums, and later tests of the suite compare two
-    runs of kernels bit for bit.  Every inactive block of the cache is claimed at its own size, largest first, zero-filled and
-    released; twice, for the fragments the first round split."""
-    import gc
-    gc.collect()
-    torch.cuda.synchronize()
-    for _ in range(2):
-        held = []
-        for seg in torch.cuda.memory_snapshot():
-            for b in seg["blocks"]:
-                if b["state"] == "inactive":
-                    held.append((b["size"], seg["segment_type"]))
-        held.sort(reverse=True)
-        keep = []
-        for size, kind in held:
-            for n in ([size] if kind == "large" or size <= (1 << 20) else [1 << 20, size - (1 << 20)]):   # a small-pool request is <= 1 MiB
-                keep.append(torch.zeros(n, dtype=torch.uint8, device=DEV))
-        torch.cuda.synchronize()
-        del keep
+        hand_the_cache_back_zeroed(DEV)   # this module's freed blocks hold random image bytes and partial sums
 
 
 def _equal(got, want, what):

@@ -833,23 +833,10 @@ _CONV_RESULTS = {}  # fill pattern -> "passed" | "FAILED" of the conv2d table
 @pytest.fixture(scope="module", autouse=True)
 def _counted_library():
     """Wrap every function of the loaded library with a counter for the duration of the module; write the profile at teardown."""
-    L = _lib()
-    lib = L.load()
-    orig = {n: getattr(lib, n) for n in L.SIGNATURES}
-
-    def wrap(name, fn):
-        def call(*a):
-            if GD._ACTIVE:
-                CALLS[name] = CALLS.get(name, 0) + 1
-            return fn(*a)
-        return call
-    for n, fn in orig.items():
-        setattr(lib, n, wrap(n, fn))
     try:
-        yield
+        with GD.counted(_lib(), CALLS):
+            yield
     finally:
-        for n, fn in orig.items():
-            setattr(lib, n, fn)
         _write_profile()
 
 

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from _headers import declared_symbols
 from anystereo.harness import scenes as H
 from anystereo.nn.liif import make_coord
 
@@ -243,11 +244,7 @@ def test_entries_refuse_before_any_launch():
     from anystereo import _scenes_lib as S
     lib = S.load()
     assert lib.scn_abi_version() == 1 and S.library_info()["matches_sources"] is True
-    declared = set()
-    for line in open(os.path.join(ROOT, "include", "anystereo_scenes.h")):
-        line = line.strip()
-        if line.endswith(("(", ",", ";")) and "scn_" in line and "(" in line and not line.startswith(("/*", "*", "#", "typedef")):
-            declared.add(line[line.index("scn_"):line.index("(")])
+    declared = declared_symbols("scenes")
     assert declared == set(S.SIGNATURES), declared ^ set(S.SIGNATURES)
     assert set(S.LAUNCHING) < set(S.SIGNATURES)
     ok = C.byref(SPEC.c_struct())

@@ -23,22 +23,8 @@ CALLS = {}  # scn_* symbol -> calls made while a guarded context was active
 @pytest.fixture(scope="module", autouse=True)
 def _counted_library():
     from anystereo import _scenes_lib as S
-    lib = S.load()
-    orig = {n: getattr(lib, n) for n in S.SIGNATURES}
-
-    def wrap(name, fn):
-        def call(*a):
-            if GD._ACTIVE:
-                CALLS[name] = CALLS.get(name, 0) + 1
-            return fn(*a)
-        return call
-    for n, fn in orig.items():
-        setattr(lib, n, wrap(n, fn))
-    try:
+    with GD.counted(S, CALLS):
         yield
-    finally:
-        for n, fn in orig.items():
-            setattr(lib, n, fn)
 
 
 # ---- device == host, bit for bit -----------------------------------------------------------------------------------------------

@@ -22,22 +22,10 @@ CALLS = {}  # spt_* symbol -> calls made while a guarded context was active
 @pytest.fixture(scope="module", autouse=True)
 def _counted_library():
     from anystereo import _spatial_lib as L
-    lib = L.load()
-    orig = {n: getattr(lib, n) for n in L.SIGNATURES}
-
-    def wrap(name, fn):
-        def call(*a):
-            if GD._ACTIVE:
-                CALLS[name] = CALLS.get(name, 0) + 1
-            return fn(*a)
-        return call
-    for n, fn in orig.items():
-        setattr(lib, n, wrap(n, fn))
     try:
-        yield
+        with GD.counted(L, CALLS):
+            yield
     finally:
-        for n, fn in orig.items():
-            setattr(lib, n, fn)
         hand_the_cache_back_zeroed(DEV)
 
 
